@@ -10,12 +10,19 @@ Default mode "fused": the K steps run in ONE launch (nmpc_closed_loop_dev), each
 scenario's closed loop on its own wavefront, so a step never waits for another
 scenario's slowest solve; for N>1 GPUs the per-step results are RCCL-gathered
 once at the end.  The one-launch-per-step mode (solve launch + shift launch,
-gather every step) is timed from the same state and reported beside it.
+gather every step) is timed from the same state and reported beside it with --full.
 
 Workload (config 3 of BASELINE.json / SURVEY.md section 8): 4096 scenarios
 per GPU, N=20, 10 static obstacles (Python/Race Track 2.py layout), T=0.2,
 fp64, the reference's IPOPT options (max_iter=100, tol 1e-8).  Weak scaling:
 per-GPU batch fixed as the GPU count grows.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything
+else the benchmark measures -- the compiled CPU baseline and its GPU-vs-CPU parity
+sample, the one-launch-per-step comparison, the config-5 side leg -- runs only with
+--full (each leg can still be dropped there: --no-cpu-baseline, --no-per-step,
+--no-config5).  --dump-outputs DIR saves what the timed path returned to its caller
+as DIR/<name>.npy, so that two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -290,13 +297,20 @@ def main():
     ap.add_argument("--mode", choices=["fused", "per_step", "cold"], default="fused",
                     help="fused: K closed-loop steps per scenario in one launch (nmpc_closed_loop_dev); "
                          "per_step: one solve launch + shift launch per step; cold: per step, u=0 each step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-per-step", action="store_true", help="skip the per-step-launch comparison line")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs: the CPU baseline with its parity sample, the per-step-launch "
+                         "comparison and the config-5 leg (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 saves what the timed path returned (per-step u0, f, status, iterations, FOV "
+                         "error, the final parameters and warm start) as DIR/<name>.npy, float64, at most "
+                         "64 MB in all (a fixed seeded sample of the scenarios beyond that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and parity sample")
+    ap.add_argument("--no-per-step", action="store_true", help="--full: skip the per-step-launch comparison line")
     ap.add_argument("--in-order", action="store_true",
                     help="fused mode: dispatch scenarios in index order (no longest-first order)")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--no-config5", action="store_true",
-                    help="skip the config-5 side leg (N=50, 10 obstacles of which 6 move; N=1 only)")
+                    help="--full: skip the config-5 side leg (N=50, 10 obstacles of which 6 move; N=1 only)")
     ap.add_argument("--config5-batch", type=int, default=8192, help="config-5 leg: scenarios (BASELINE config 5)")
     ap.add_argument("--config5-cpu-scenarios", type=int, default=2048,
                     help="config-5 leg: scenarios in the CPU baseline's bounded sample")
@@ -307,6 +321,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit(f"bench.py: --gpus must be >= 1 (got {args.gpus})")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"bench.py: --steps must be >= 1 and --warmup >= 0 (got {args.steps}, {args.warmup})")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         # no launcher around us: start the N rank processes ourselves (before any GPU call
@@ -327,9 +343,9 @@ def main():
     spec = config_spec(args.config)
     B, K, W = args.batch, args.steps, args.warmup
     # the config-5 side leg (BASELINE config 5, Dynamic Obstacle avoidance.m:211-231): N=1 only
-    leg5 = world == 1 and args.config != 5 and args.mode == "fused" and not args.no_config5
+    leg5 = args.full and world == 1 and args.config != 5 and args.mode == "fused" and not args.no_config5
     cpu_res = cpu5 = None
-    if world == 1 and not args.no_cpu_baseline:  # OpenMP threads, before the GPU is initialised
+    if args.full and world == 1 and not args.no_cpu_baseline:  # OpenMP threads, before the GPU is initialised
         lb = spec.bounds()
         cpu_res = cpu_baseline(spec, args.config, draw_scenarios(spec, B, seed=1000 + args.config), *lb, K, W,
                                p_step=obstacle_pstep(spec, W + K), budget_s=args.cpu_budget)
@@ -352,8 +368,9 @@ def main():
     dev = torch.device("cuda", dev_idx)
     ctx = dict(world=world, rank=rank, backend=backend, dev=dev, dist=dist)
 
-    m = measure(args, ctx, args.config, B, K, W, args.mode, per_step_side=(args.mode == "fused" and not args.no_per_step),
-                dump_rows=args.dump_rows)
+    m = measure(args, ctx, args.config, B, K, W, args.mode,
+                per_step_side=(args.full and args.mode == "fused" and not args.no_per_step),
+                dump_rows=args.dump_rows, dump_outputs=args.dump_outputs if rank == 0 else "")
     m5 = measure(args, ctx, 5, args.config5_batch, K, W, "fused", per_step_side=False) if leg5 else None
 
     if rank == 0:
@@ -395,7 +412,28 @@ def obstacle_pstep(spec, n):
     return obstacle_steps(195, n, spec.np)
 
 
-def measure(args, ctx, cfg, B, K, W, mode, per_step_side=False, dump_rows=""):
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_arrays(outdir, arrs, B, max_bytes=DUMP_MAX_BYTES - 10 ** 6):
+    """--dump-outputs: save each device tensor of `arrs` (name -> (tensor, scenario axis)) as
+    outdir/<name>.npy in float64.  When all B scenarios would take more than max_bytes (a
+    megabyte under the 64 MB limit, for the .npy headers and the index), every array keeps the
+    same fixed sample of the scenarios (seeded, ascending; saved as scenario_index.npy)."""
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    per_scn = sum(8 * t.numel() // B for t, _ in arrs.values()) + 8
+    keep = np.arange(B)
+    if per_scn * B > max_bytes:
+        keep = np.sort(np.random.default_rng(20240607).choice(B, size=max(1, max_bytes // per_scn), replace=False))
+    idx = torch.as_tensor(keep, device=next(iter(arrs.values()))[0].device)
+    for name, (t, axis) in arrs.items():
+        np.save(os.path.join(outdir, name + ".npy"),
+                t.index_select(axis, idx).to(torch.float64).cpu().numpy())
+    np.save(os.path.join(outdir, "scenario_index.npy"), keep.astype(np.float64))
+
+
+def measure(args, ctx, cfg, B, K, W, mode, per_step_side=False, dump_rows="", dump_outputs=""):
     """One configuration on this rank's GPU: W warm-up MPC steps, then exactly K timed steps
     bracketed by barrier + synchronize (fused: one launch, timed twice over -- once on scratch
     copies of the same state, then the timed launch); HIP events on the launch stream give the
@@ -475,7 +513,7 @@ def measure(args, ctx, cfg, B, K, W, mode, per_step_side=False, dump_rows=""):
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed_run(mode, p, w):
+    def timed_run(mode, p, w, dump=""):
         """Warmup W steps (advancing the closed loop), then time exactly K steps."""
         hw, ht = hist_bufs(max(W, 1)), hist_bufs(K)
         # warmup: W MPC steps advance the closed loop (one solve + shift launch per step)
@@ -513,9 +551,19 @@ def measure(args, ctx, cfg, B, K, W, mode, per_step_side=False, dump_rows=""):
         hist = {int(s_): int((sts == s_).sum()) for s_ in np.unique(sts)}
         timed_run.fov = float(ht["fov"].mean().item())
         timed_run.chain = ht["iters"].sum(0).cpu().numpy()
+        if dump:
+            # what the timed path handed back: every timed step's rows (the last step is row K-1)
+            # and the closed-loop state it left behind; scenarios on axis 1 of the (K, B, ...) rows
+            arrs = {"u": (ht["u"], 1), "f": (ht["f"], 1), "status": (ht["status"], 1), "iters": (ht["iters"], 1),
+                    "p_final": (p, 0), "w_final": (w, 0)}
+            if mode == "fused":
+                arrs["fov"] = (ht["fov"], 1)
+            else:
+                arrs["x_last"] = (out["x"], 0)
+            dump_arrays(dump, arrs, B)
         return float(el_t.item()), kern_ms, float(tot[0].item() / tot[1].item()), hist
 
-    elapsed, kern_ms, ibar, status_hist = timed_run(mode, p0.clone(), w0.clone())
+    elapsed, kern_ms, ibar, status_hist = timed_run(mode, p0.clone(), w0.clone(), dump=dump_outputs)
     res = {"cfg": cfg, "spec": spec, "B": B, "K": K, "W": W, "mode": mode, "elapsed": elapsed, "kern_ms": kern_ms,
            "ibar": ibar, "status_hist": status_hist, "solver": solver, "bnd": bnd, "ps_np": ps_np,
            "pstep": pstep, "fov": timed_run.fov if mode == "fused" else None,

@@ -12,7 +12,7 @@ if [ -n "$AB_DUMP" ]; then
 fi
 for rep in ${AB_REPS:-1 2}; do
   for v in "$@"; do
-    NMPC_LIB=$PWD/variants/$v.so timeout -k 10 200 python -u bench.py --no-per-step --no-cpu-baseline ${BENCH_ARGS:-} > $O/${TAG}_${v}_${rep}.json 2> $O/${TAG}_${v}_${rep}.err || exit $?
+    NMPC_LIB=$PWD/variants/$v.so timeout -k 10 200 python -u bench.py --full --no-per-step --no-cpu-baseline ${BENCH_ARGS:-} > $O/${TAG}_${v}_${rep}.json 2> $O/${TAG}_${v}_${rep}.err || exit $?
   done
 done
 echo ab bench done

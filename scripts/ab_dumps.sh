@@ -8,6 +8,6 @@ for v in "$@"; do
   python scripts/ab_bitwise.py --compare /tmp/ab_prod.npz /tmp/ab_$v.npz > $O/${TAG}_${v}_cmp.txt 2>&1
 done
 for v in $BENCH_V; do
-  NMPC_LIB=$PWD/variants/$v.so timeout -k 10 200 python -u bench.py --no-per-step --no-cpu-baseline > $O/${TAG}_${v}_bench.json 2> $O/${TAG}_${v}_bench.err || exit $?
+  NMPC_LIB=$PWD/variants/$v.so timeout -k 10 200 python -u bench.py --full --no-per-step --no-cpu-baseline > $O/${TAG}_${v}_bench.json 2> $O/${TAG}_${v}_bench.err || exit $?
 done
 echo dumps done

@@ -12,9 +12,9 @@ for v in "$@"; do
   python scripts/ab_bitwise.py --compare /tmp/ab_prod.npz /tmp/ab_$v.npz > $O/${TAG}_${v}_cmp.txt 2>&1
 done
 for rep in 1 2 3; do
-  timeout -k 10 200 python -u bench.py --no-per-step --no-cpu-baseline ${BENCH_ARGS:-} > $O/${TAG}_prod_${rep}.json 2> $O/${TAG}_prod_${rep}.err || exit $?
+  timeout -k 10 200 python -u bench.py --full --no-per-step --no-cpu-baseline ${BENCH_ARGS:-} > $O/${TAG}_prod_${rep}.json 2> $O/${TAG}_prod_${rep}.err || exit $?
   for v in "$@"; do
-    NMPC_LIB=$PWD/variants/$v.so timeout -k 10 200 python -u bench.py --no-per-step --no-cpu-baseline ${BENCH_ARGS:-} > $O/${TAG}_${v}_${rep}.json 2> $O/${TAG}_${v}_${rep}.err || exit $?
+    NMPC_LIB=$PWD/variants/$v.so timeout -k 10 200 python -u bench.py --full --no-per-step --no-cpu-baseline ${BENCH_ARGS:-} > $O/${TAG}_${v}_${rep}.json 2> $O/${TAG}_${v}_${rep}.err || exit $?
   done
 done
 echo ab round done

@@ -3,7 +3,7 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 O=gpurun_out; T=$1; L=$PWD/$2; LS=${3:+$PWD/$3}
-NMPC_LIB=$L timeout -k 10 300 python -u bench.py --no-per-step --no-cpu-baseline > $O/${T}_bench.json 2> $O/${T}_bench.err || exit $?
+NMPC_LIB=$L timeout -k 10 300 python -u bench.py --full --no-per-step --no-cpu-baseline > $O/${T}_bench.json 2> $O/${T}_bench.err || exit $?
 if [ -n "$LS" ]; then
   NMPC_LIB=$LS timeout -k 10 200 python -u scripts/phase_profile.py 3 1024 > $O/${T}_phase.log 2>&1 || exit $?
   NMPC_LIB=$LS timeout -k 10 200 python -u scripts/resto_profile.py 1024 > $O/${T}_resto.log 2>&1 || exit $?

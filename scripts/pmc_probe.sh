@@ -2,7 +2,7 @@
 set -o pipefail
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --no-cpu-baseline --no-per-step"
+B="$R/bench.py --full --no-cpu-baseline --no-per-step"
 PMC=${PMC:-"SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH"}
 T=${1:-icache}
 timeout -s KILL 200 rocprofv3 --pmc $PMC -d $R/gpurun_out/prof_$T -o run -- python3 $B > $R/gpurun_out/prof_$T.log 2>&1

@@ -14,14 +14,14 @@ for v in "$@"; do
   python scripts/ab_bitwise.py --compare /tmp/ab5_prod.npz /tmp/ab5_$v.npz > $O/${TAG}_${v}_cmp5.txt 2>&1
 done
 for rep in ${AB_REPS:-1 2}; do
-  timeout -k 10 200 python -u bench.py --no-per-step --no-cpu-baseline > $O/${TAG}_prod_${rep}.json 2> $O/${TAG}_prod_${rep}.err || exit $?
+  timeout -k 10 200 python -u bench.py --full --no-per-step --no-cpu-baseline > $O/${TAG}_prod_${rep}.json 2> $O/${TAG}_prod_${rep}.err || exit $?
   for v in "$@"; do
-    NMPC_LIB=$PWD/variants/$v.so timeout -k 10 200 python -u bench.py --no-per-step --no-cpu-baseline > $O/${TAG}_${v}_${rep}.json 2> $O/${TAG}_${v}_${rep}.err || exit $?
+    NMPC_LIB=$PWD/variants/$v.so timeout -k 10 200 python -u bench.py --full --no-per-step --no-cpu-baseline > $O/${TAG}_${v}_${rep}.json 2> $O/${TAG}_${v}_${rep}.err || exit $?
   done
 done
-timeout -k 10 200 python -u bench.py --no-per-step --no-cpu-baseline --batch 16384 > $O/${TAG}_prod_wb.json 2> $O/${TAG}_prod_wb.err || exit $?
+timeout -k 10 200 python -u bench.py --full --no-per-step --no-cpu-baseline --batch 16384 > $O/${TAG}_prod_wb.json 2> $O/${TAG}_prod_wb.err || exit $?
 for v in "$@"; do
-  NMPC_LIB=$PWD/variants/$v.so timeout -k 10 200 python -u bench.py --no-per-step --no-cpu-baseline --batch 16384 > $O/${TAG}_${v}_wb.json 2> $O/${TAG}_${v}_wb.err || exit $?
+  NMPC_LIB=$PWD/variants/$v.so timeout -k 10 200 python -u bench.py --full --no-per-step --no-cpu-baseline --batch 16384 > $O/${TAG}_${v}_wb.json 2> $O/${TAG}_${v}_wb.err || exit $?
 done
 echo ab done
 # the bounding chain alone (trace on), product and variants

@@ -3,6 +3,6 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 O=gpurun_out; TAG=${1:-r05}
-timeout -k 10 300 python -u bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || exit 1
+timeout -k 10 300 python -u bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || exit 1
 bash scripts/profile_round.sh $TAG || exit 1
 echo measure done

@@ -10,7 +10,7 @@ if [ "$1" == "a" ]; then
   rc=$?; echo "tests rc=$rc"
   [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
   timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/${TAG}_smoke.log 2>&1 || exit $?
-  timeout -k 10 400 python -u bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || exit $?
+  timeout -k 10 400 python -u bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || exit $?
   echo bench done
   bash scripts/profile_round.sh $TAG || exit 1
   echo "part a done tests_rc=$rc"

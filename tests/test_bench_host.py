@@ -74,6 +74,39 @@ def test_launch_ranks_relays_rank0_line(bench, monkeypatch, capsys):
     assert bench.launch_ranks(2, []) == 3
 
 
+def test_dump_arrays_keeps_a_fixed_sample_under_the_size_limit(bench, tmp_path):
+    """--dump-outputs: float64 .npy files; over the limit every array keeps the same seeded
+    sample of the scenarios (ascending, recorded), the same from run to run."""
+    import torch
+    B, K = 50, 3
+    arrs = {"u": (torch.arange(K * B * 6, dtype=torch.float64).reshape(K, B, 6), 1),
+            "status": (torch.arange(K * B, dtype=torch.int32).reshape(K, B), 1),
+            "w_final": (torch.arange(B * 7, dtype=torch.float64).reshape(B, 7), 0)}
+    per_scn = 8 * (K * 6 + K + 7) + 8
+    for d, limit in (("all", per_scn * B), ("s1", per_scn * 20 + 5), ("s2", per_scn * 20 + 5)):
+        bench.dump_arrays(str(tmp_path / d), arrs, B, max_bytes=limit)
+    full = {n: np.load(tmp_path / "all" / f"{n}.npy") for n in ("u", "status", "w_final", "scenario_index")}
+    np.testing.assert_array_equal(full["scenario_index"], np.arange(B))
+    assert all(v.dtype == np.float64 for v in full.values())
+    for n, (t, _) in arrs.items():
+        np.testing.assert_array_equal(full[n], t.numpy())
+    idx = np.load(tmp_path / "s1" / "scenario_index.npy").astype(int)
+    assert len(idx) == 20 and np.all(np.diff(idx) > 0) and idx.max() < B
+    np.testing.assert_array_equal(np.load(tmp_path / "s1" / "u.npy"), full["u"][:, idx])
+    np.testing.assert_array_equal(np.load(tmp_path / "s1" / "status.npy"), full["status"][:, idx])
+    np.testing.assert_array_equal(np.load(tmp_path / "s1" / "w_final.npy"), full["w_final"][idx])
+    for n in os.listdir(tmp_path / "s1"):
+        np.testing.assert_array_equal(np.load(tmp_path / "s1" / n), np.load(tmp_path / "s2" / n))
+    assert sum(np.load(tmp_path / "s1" / n).nbytes for n in os.listdir(tmp_path / "s1")) <= per_scn * 20 + 5
+
+
+def test_steps_and_warmup_are_validated():
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
 def test_gpus_must_match_launcher_world_size():
     """Under a launcher, --gpus must equal WORLD_SIZE (checked before any GPU call)."""
     import subprocess
