@@ -161,7 +161,9 @@ int nmpc_solve_batch(nmpc_handle* h, int32_t B,
  * of the problem's class and the equality class run.  The equality class needs its
  * workspace reserved for B scenarios beforehand (nmpc_reserve_eq); without it a batch that
  * has equality rows is not solved and every scenario reports NMPC_STATUS_EQ_UNRESERVED
- * (x_out and f NaN).  Batches without equality rows need no reservation. */
+ * with iters 0 and NaN in f and in every output vector passed (x_out, g_out, lam_x_out,
+ * lam_g_out, lam_p_out, X_out), so none keeps an earlier call's values.  Batches without
+ * equality rows need no reservation. */
 int nmpc_solve_batch_dev(nmpc_handle* h, int32_t B,
                          const double* x0, int64_t ld_x0,
                          const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx,

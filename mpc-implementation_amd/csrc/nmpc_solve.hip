@@ -273,8 +273,20 @@ __device__ __forceinline__ double wsum(double v) {
 // operations, the row passes' largest cost).  The result differs from the sum of the
 // logarithms at the rounding level only: the product carries <= n ulp of relative error
 // (n factors per lane, <= 24), i.e. <= 3e-15 absolute in the lane's log sum, below the
-// rounding of the sum it replaces.  A non-positive argument gives log(<= 0) = NaN / -inf
-// as the sum did, so a trial outside the bounds is still rejected as non-finite.
+// rounding of the sum it replaces.  A zero argument gives -inf and a NaN argument NaN, as
+// the sum did, so such a trial is still rejected as non-finite.
+// PRECONDITION: at most one negative argument per lane.  One negative argument gives
+// log(< 0) = NaN as the sum did; the signs of two cancel in the product and the lane returns
+// a finite value.  The callers meet it: every argument is a slack of the current or a trial
+// point (s - lo, hi - s, p, n), and every trial step is cut by the fraction to the boundary,
+// which keeps all of them positive.
+// (A per-lane sign flag costs 0.8 % of config 3's throughput, against a run-to-run spread
+// of 0.3 %: measured and not kept)
+// mul2 -- the only form the solver calls -- takes the mantissa of its first argument BEFORE
+// multiplying, so the pair's product can neither overflow nor underflow for any normal second
+// argument (1e-160 * 1e-170 gives the finite sum of the logarithms, not log 0); the product
+// mant(x) * y is an exact scaling of x * y, so where x * y is a normal number the result is
+// bitwise what x * y renormalised gave.  mul forms m * x with m in [0.5, 1).
 struct LogAcc {
   double m = 1.0;
   int e = 0;
@@ -283,11 +295,11 @@ struct LogAcc {
     m = __builtin_amdgcn_frexp_mant(p);
     e += __builtin_amdgcn_frexp_exp(p);
   }
-  // two factors: their product first (|x|, |y| < 2^500: no overflow), one renormalisation
+  // two factors: mant(x) * y first (mant(x) in [0.5, 1)), one renormalisation
   __device__ __forceinline__ void mul2(double x, double y) {
-    const double xy = x * y;
+    const double xy = __builtin_amdgcn_frexp_mant(x) * y;
     const double xe = __builtin_amdgcn_frexp_mant(xy);
-    const int ee = __builtin_amdgcn_frexp_exp(xy);
+    const int ee = __builtin_amdgcn_frexp_exp(x) + __builtin_amdgcn_frexp_exp(xy);
     const double p = m * xe;
     m = __builtin_amdgcn_frexp_mant(p);
     e += ee + __builtin_amdgcn_frexp_exp(p);
@@ -336,8 +348,14 @@ __device__ __forceinline__ float rsq(float x) { return __builtin_amdgcn_rsqf(x);
 // bitwise a / b for finite non-zero operands of moderate range -- slacks, multipliers,
 // pivots, distances, step components -- which is what every call site divides; where a
 // caller's operand can be 0 or inf (a missing bound, a zero step component) its result is
-// discarded by the caller's guard, as a / b's was.  Three fewer instructions per division,
-// two of them on the dependence chain.  NMPC_FDIV=0: plain a / b.
+// discarded by the caller's guard, as a / b's was.  Tested against the IEEE quotient
+// (tests/test_gpu_primitives.py; domain map in DESIGN.md 11): equal wherever the exponent of
+// a is >= -969 (the correction's residual ~2^-53 |a| stays normal) and a / b does not
+// overflow; a zero numerator gives 0; a zero or infinite b, or a NaN, gives NaN (a / b:
+// +-inf or 0) -- so an unguarded site needs b finite and non-zero, or a consumer for which
+// NaN and +-inf are the same (a non-finite value that fails the next finiteness test).
+// Three fewer instructions per division, two of them on the dependence chain (DESIGN.md 9,
+// round 6).  NMPC_FDIV=0: plain a / b.
 #ifndef NMPC_FDIV
 #define NMPC_FDIV 1
 #endif
@@ -730,7 +748,10 @@ struct Solver {
     const double c7 = cos(x[7]), s7 = sin(x[7]);
     const double a2 = a * a, b2 = bb * bb;
     // (the compiler's divisions: with qd() the objective value moved in its last bit at a few
-    // points of the round-6 bitwise A/B -- cause not isolated -- so they stay)
+    // points of the round-6 bitwise A/B, so they stay.  The quotient itself is not the cause:
+    // on these operand shapes -- c^2, s^2 and 1 over a^2 and over b^2, for the model's heights,
+    // angles and both fields of view -- qd() is bitwise a / b (tests/test_gpu_primitives.py), which
+    // leaves the contraction of the surrounding sums around qd's final fma as the suspect)
     const double A = (c7 * c7) / a2 + (s7 * s7) / b2;
     const double Bq = 2 * c7 * s7 * ((1 / a2) - (1 / b2));
     const double C = (s7 * s7) / a2 + (c7 * c7) / b2;
@@ -995,6 +1016,10 @@ struct Solver {
         const double r1 = c * ex + sn * ey;
         const double r2 = sn * ex - c * ey;
         double u1[6], u2[6], gr1[6], gr2[6], ge1[6], ge2[6];
+        // (qd unguarded: a = z al6, bb = z al5 are zero only at z = 0 or a zero FOV, where the
+        // plain quotient's inf makes the objective and this gradient non-finite as qd's NaN
+        // does, and both fail the same finiteness tests; 1 / b is in qd's domain for every
+        // finite non-zero b)
         const double ia = qd(1.0, a), ib = qd(1.0, bb);
         const double e1 = r1 * ia, e2 = r2 * ib;
 #pragma unroll
@@ -1008,6 +1033,8 @@ struct Solver {
         }
         const double ddx = x - xt, ddy = yy - yt;
         const double dd = TC ? tk[10] : sqrt(ddx * ddx + ddy * ddy);
+        // (qd unguarded: dd = 0 only with the UAV exactly over the target, where 1 / 0 = inf gives
+        // 0 * inf = NaN in g6[0..1] below just as qd's NaN does: Invalid_Number either way)
         const double idd = qd(1.0, dd);
         const double id3 = idd * idd * idd;
         const double w1 = rvars[30], w2 = rvars[31];  // this scenario's cost weights
@@ -2471,6 +2498,9 @@ struct Solver {
     row_rs(r, D, rs);
     const double kd = P->o.kappa_d;
     const double pr = pR[r], nr = nR[r];
+    // (qd unguarded: p, n > 0 are kept off zero by the fraction to the boundary and are
+    // normal numbers, Sp, Sn >= delta_x-regularised z / p > 0, and 1 + D (..) >= 1: finite,
+    // non-zero denominators under a numerator of 1, inside qd's domain)
     const double ip = qd(1.0, pr), in_ = qd(1.0, nr);
     Sp = zpR[r] * ip + delta;
     Sn = znR[r] * in_ + delta;
@@ -2488,7 +2518,7 @@ struct Solver {
   }
   __device__ __forceinline__ double dr2(int i) const {  // D_R^2 = 1/max(1,|x_R|)^2
     const double a = fmax(1.0, fabs(UR[i]));
-    return qd(1.0, a * a);
+    return qd(1.0, a * a);  // a * a in [1, inf): in qd's domain unless UR is inf / NaN, which is non-finite either way
   }
   // restoration step rows: dy, dp, dn, ds (= J dx + c - dp + dn); for the Newton
   // direction also theta_R and the slack/p/n part of grad(phi_R)^T d
@@ -2535,8 +2565,9 @@ struct Solver {
       }
       if (!soc) {
         // (plain divisions here: with qd() these two lines alone change the restoration
-        // line search's results -- the one place the bitwise A/B of round 6 found one, cause
-        // not isolated -- so they keep the compiler's division)
+        // line search's results -- the one place the bitwise A/B of round 6 found one -- so
+        // they keep the compiler's division.  qd() is bitwise a / b on mu / (s - lo), mu / (hi - s),
+        // mu / p and mu / n operands (tests/test_gpu_primitives.py), so the quotient is not the cause)
         const double gs = -(hl ? mu / (sr - lo) : 0.0) + (hu ? mu / (hi - sr) : 0.0) +
                           kd * mu * ((hl && !hu ? 1.0 : 0.0) - (hu && !hl ? 1.0 : 0.0));
         const double gr = gs * dsv + (rho - mu / pr + kd * mu) * dpv + (rho - mu / nr + kd * mu) * dnv;
@@ -4953,9 +4984,11 @@ __global__ void nmpc_eq_scan_kernel(long long n, int ng, const double* lbg, long
 // a device-pointer solve whose batch has equality rows while the equality class's
 // workspace is not reserved (nmpc_reserve_eq): neither class of the pair ran, so every
 // scenario reports NMPC_STATUS_EQ_UNRESERVED (IPOPT Insufficient_Memory) with a NaN
-// objective and solution (no-op when the flag is 0: the problem's class ran)
-__global__ void nmpc_eq_unreserved_kernel(int B, const int* flag, int nw, double* x_out, double* f_out,
-                                          int* status, int* iters) {
+// objective and NaN in every output vector the caller passed, so nothing keeps an earlier
+// call's values (no-op when the flag is 0: the problem's class ran)
+__global__ void nmpc_eq_unreserved_kernel(int B, const int* flag, int nw, int ng, int np, int nX, double* x_out,
+                                          double* f_out, double* g_out, double* lam_x, double* lam_g, double* lam_p,
+                                          double* X_out, int* status, int* iters) {
   if (*flag == 0) return;
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
@@ -4964,6 +4997,16 @@ __global__ void nmpc_eq_unreserved_kernel(int B, const int* flag, int nw, double
   if (iters) iters[b] = 0;
   if (f_out) f_out[b] = nan;
   for (int i = 0; i < nw; ++i) x_out[(long long)b * nw + i] = nan;
+  if (lam_x)
+    for (int i = 0; i < nw; ++i) lam_x[(long long)b * nw + i] = nan;
+  for (int i = 0; i < ng; ++i) {
+    if (g_out) g_out[(long long)b * ng + i] = nan;
+    if (lam_g) lam_g[(long long)b * ng + i] = nan;
+  }
+  if (lam_p)
+    for (int i = 0; i < np; ++i) lam_p[(long long)b * np + i] = nan;
+  if (X_out)
+    for (int i = 0; i < nX; ++i) X_out[(long long)b * nX + i] = nan;
 }
 
 // completion-guard state of a one-workgroup-per-scenario launch (no queues)
@@ -5091,8 +5134,10 @@ ClassFns nmpc_class_fns_A32() { return class_fns<CapA32>(); }
 ClassFns nmpc_class_fns_C32() { return class_fns<CapC32>(); }
 #elif NMPC_TU_CLASS == 6
 ClassFns nmpc_class_fns_D() { return class_fns<CapD>(); }
-#else
+#elif NMPC_TU_CLASS == 7
 ClassFns nmpc_class_fns_E() { return class_fns<CapE>(); }
+#elif NMPC_TU_CLASS != 0  // 0: no class and no C-ABI (a unit that includes this file for its device functions)
+#error "NMPC_TU_CLASS must be 0 (no class) or 1..7 (A, B, C, A32, C32, D, E)"
 #endif
 #else  // host translation unit
 
@@ -5505,7 +5550,8 @@ static int solve_dev(nmpc_handle* h, int32_t B, const double* x0, int64_t ld_x0,
                        (const Params*)h->dprm, (int)B, ioE);
   if (run.Enows)
     hipLaunchKernelGGL(nmpc_eq_unreserved_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, (int)B,
-                       (const int*)h->deq, P.nwE, x_out, f_out, status, iters);
+                       (const int*)h->deq, P.nwE, P.ng, P.npE, P.nxE * (P.N + 1), x_out, f_out, g_out, lam_x_out,
+                       lam_g_out, lam_p_out, X_out, status, iters);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
   return NMPC_OK;

@@ -227,7 +227,7 @@ def test_equality_workspace_is_allocated_lazily():
     have none holds its class's ~120 KB per scenario only.
     Device-pointer batches never allocate it (they never synchronise the host): without it a
     batch with equality rows reports NMPC_STATUS_EQ_UNRESERVED (-102) per scenario with NaN x
-    and f, and a closed loop raises (scheduler_error bit 4); after reserve_equality(B) it
+    and f, and a closed loop raises (scheduler_error bit 2, value 4); after reserve_equality(B) it
     is solved, and a batch without equality rows gives bitwise the same results either way.
     The host-array call allocates it on demand, and an equality batch through the device path
     equals the host path's solve of it."""
@@ -294,3 +294,31 @@ def test_equality_workspace_is_allocated_lazily():
     assert s2.memory_info()["ws_eq_bytes"] == s2.memory_info()["ws_eq_per_scenario"]
     np.testing.assert_array_equal(h2["x"], h["x"])
     assert abs(float(h["g"].ravel()[row]) - lbg[row]) <= 1e-6
+
+
+def test_unreserved_equality_batch_leaves_no_stale_output():
+    """A device-pointer batch with equality rows and no reserved workspace runs neither class:
+    every output the caller passed (x, f, g, lam_x, lam_g, lam_p, X) must come back NaN, not
+    with an earlier call's values, and status / iters as documented (-102 / 0)."""
+    import torch
+    from nmpc_amd import nlpsol, make_spec, REFERENCE_OPTS
+    from nmpc_amd._lib import EQ_UNRESERVED
+
+    f64 = dict(dtype=torch.float64, device="cuda")
+    prob, p, lbx, ubx, lbg, ubg, row = _pinned_z_problem(0)
+    spec = make_spec("race_track_2", N=8, T=0.2)
+    s = nlpsol("solver", "ipopt", spec, REFERENCE_OPTS)
+    Bs, SENT = 3, 777.25
+    sizes = {"x": spec.nw, "g": spec.ng, "lam_x": spec.nw, "lam_g": spec.ng, "lam_p": spec.np, "X": spec.nX}
+    out = {k: torch.full((Bs, n), SENT, **f64) for k, n in sizes.items()}
+    out["f"] = torch.full((Bs,), SENT, **f64)
+    out["status"] = torch.full((Bs,), 55, dtype=torch.int32, device="cuda")
+    out["iters"] = torch.full((Bs,), 55, dtype=torch.int32, device="cuda")
+    b = [torch.tensor(v, **f64) for v in (lbx, ubx, lbg, ubg)]
+    s.solve_device(torch.zeros(Bs, prob.nw, **f64), *b, torch.tensor(np.tile(p, (Bs, 1)), **f64), out)
+    torch.cuda.synchronize()
+    assert s.memory_info()["ws_eq_bytes"] == 0
+    got = {k: v.cpu().numpy() for k, v in out.items()}
+    assert np.all(got["status"] == EQ_UNRESERVED) and np.all(got["iters"] == 0)
+    for k in ("x", "f", "g", "lam_x", "lam_g", "lam_p", "X"):
+        assert np.all(np.isnan(got[k])), (k, got[k].ravel()[:6])

@@ -286,3 +286,37 @@ def test_oracle_records_restoration_checks():
     assert r["status"] == orc.INFEASIBLE_PROBLEM_DETECTED and r["iter"] == z["iter"][k]
     assert res and res[-1]["it"] == r["iter"] and res[-1]["err"] <= tol
     assert all(c["err"] > tol for c in res[:-1] if c["it"] < r["iter"] - 1) or len(res) == 1
+
+
+# ---- first-iterations trace comparator (tests/trace_cases.py, tests/golden/trace_spread.npz):
+# the CPU half of tests/test_gpu_trace.py
+@pytest.mark.parametrize("name", list(__import__("tests.trace_cases", fromlist=["CASES"]).GATED))
+def test_trace_comparator_passes_rounding_variants_and_catches_1e7_errors(name):
+    """Under the comparator the GPU trace is held to, (a) every rounding variant of the oracle
+    passes against the plain oracle, and (b) an oracle with a 1e-7 relative error in the
+    stage-cost gradient, in one obstacle row's gradient, in the Newton step or in the stage-cost
+    Hessian fails on some field of the case by at least 10 x the tolerance."""
+    from tests import trace_cases as tc
+    fix = np.load(tc.FIXTURE)
+    case = tc.build_case(name)
+    for b in (0, 1):
+        rows, chk, status, _ = tc.oracle_trace(case, b)
+        # the plain oracle run here against the stored one: equal up to the BLAS build and its
+        # thread count (the generator pins one thread), far inside the tolerance
+        ratios = tc.compare(fix, name, b, rows, chk)[1]
+        assert max(ratios.values()) <= 1.0, (b, ratios)
+        assert int(fix[f"{name}__{b}__lead"]) >= 4, "too few comparable iterations"
+        for v in tc.VARIANTS:
+            vr, vc = tc.oracle_trace(case, b, v)[:2]
+            ratios = tc.compare(fix, name, b, vr, vc)[1]
+            assert max(ratios.values()) <= 1.0, (b, v, ratios)
+    for mut in tc.MUTATIONS:
+        if not tc.applies(mut, case):
+            continue
+        worst = {}
+        for b in (0, 1):
+            ratios = tc.compare(fix, name, b, *tc.mutated_trace(name, case, b, mut))[1]
+            f = max(ratios, key=ratios.get)
+            worst[b] = (f, ratios[f])
+        print(f"{name} {mut}: {worst}")
+        assert max(r for _, r in worst.values()) >= tc.MARGIN, (mut, worst)
