@@ -183,6 +183,58 @@ int nmpc_solve_batch_dev(nmpc_handle* h, int32_t B,
  * synchronise the host; nmpc_solve_batch allocates it on demand. */
 int nmpc_reserve_eq(nmpc_handle* h, int32_t B);
 
+/* Evaluation of the NLP's function layer at GIVEN points, for B scenarios at once: CasADi's
+ * nlp_f / nlp_g / nlp_grad_f of an nlpsol object and ff(u, p) of Python/NMPC_TT.py:368, plus
+ * a first-order (KKT) certificate that does not come from the solver.  x is any decision
+ * vector (a policy's output, a perturbed or shifted plan, a solve's x_out).  No options,
+ * problem classes or statuses are involved; non-finite inputs give non-finite outputs.
+ *
+ * DEVICE pointers, enqueued on `stream`; never synchronises and allocates nothing once the
+ * handle's workspace covers B (the solve's workspace serves: a handle that has solved a
+ * batch of B evaluates B without allocating).  Layouts, leading-dimension-0 broadcast and
+ * |b| >= 1e19 = no bound exactly as nmpc_solve_batch.
+ *   x (nw x B) and p (np x B) are required.
+ *   lam_g (ng x B), lam_x (nw x B): multipliers in CasADi's sign convention (at a solution
+ *     grad f + J_g^T lam_g + lam_x = 0, lam > 0 on an upper bound); NULL = zeros.
+ *   lbx, ubx, lbg, ubg: only kkt_out reads them; NULL unless kkt_out is given.
+ * Every output may be NULL, at least one must not be:
+ *   f_out (B), g_out (ng x B), X_out (nx(N+1) x B) as nmpc_solve_batch's;
+ *   grad_f_out (nw x B) = grad_w f;
+ *   grad_l_out (nw x B) = grad_w f + J_g^T lam_g + lam_x (== grad_f_out bitwise without
+ *     multipliers);
+ *   kkt_out (5 x B), unnormalised, per scenario
+ *     [0] stat  = |grad_l|_inf
+ *     [1] gmax  = |grad_f|_inf
+ *     [2] viol  = max(0, g - ubg, lbg - g, x - ubx, lbx - x) over the bounds present
+ *     [3] compl = max over rows and variables of |lam| * gap, the gap taken towards the upper
+ *                 bound where lam > 0 and towards the lower bound where lam < 0; a multiplier
+ *                 that points at an absent bound contributes 0
+ *     [4] lmax  = max(|lam_g|_inf, |lam_x|_inf)
+ *     (a NaN in any term makes that entry NaN).  IPOPT's unscaled acceptance test read on
+ *     g(x) is stat <= dual_inf_tol, viol <= constr_viol_tol, compl <= compl_inf_tol (1 + lmax).
+ * f sums the stages 0..N-1; stage 0 is constant in w, so its derivative terms are
+ * structurally absent (with N = 1, grad_f is exactly 0).  Fixed variables and equality rows
+ * need no special case: the bounds only enter viol and compl.
+ * B <= 0, a NULL x or p, every output NULL, kkt_out with a bound missing, or a leading
+ * dimension that is neither 0 nor >= the vector length return NMPC_E_INVALID before any
+ * device call. */
+int nmpc_eval_batch_dev(nmpc_handle* h, int32_t B,
+                        const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                        const double* lam_g, int64_t ld_lam_g, const double* lam_x, int64_t ld_lam_x,
+                        const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx,
+                        const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg,
+                        double* f_out, double* g_out, double* X_out,
+                        double* grad_f_out, double* grad_l_out, double* kkt_out, void* stream);
+
+/* Same with HOST pointers; synchronous (staged through the handle's device buffer). */
+int nmpc_eval_batch(nmpc_handle* h, int32_t B,
+                    const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                    const double* lam_g, int64_t ld_lam_g, const double* lam_x, int64_t ld_lam_x,
+                    const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx,
+                    const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg,
+                    double* f_out, double* g_out, double* X_out,
+                    double* grad_f_out, double* grad_l_out, double* kkt_out);
+
 /* Optional per-iteration trace (debugging / parity): when enabled, the next
  * solve records NMPC_TRACE_FIELDS doubles per iteration per scenario into a
  * device buffer readable with nmpc_read_trace (host pointer,

@@ -5141,6 +5141,8 @@ ClassFns nmpc_class_fns_E() { return class_fns<CapE>(); }
 #endif
 #else  // host translation unit
 
+#include "nmpc_eval.h"  // the evaluation kernel's translation unit (nmpc_eval.hip)
+
 struct nmpc_handle {
   Params hp;
   Params* dprm = nullptr;
@@ -5636,6 +5638,106 @@ int nmpc_solve_batch(nmpc_handle* h, int32_t B, const double* x0, int64_t ld_x0,
   down(X_out, d_X, (size_t)B * nX * 8); down(f_out, d_f, (size_t)B * 8);
   down(lam_p_out, d_lp, (size_t)B * np * 8);
   down(status, d_st, (size_t)B * 4); down(iters, d_it, (size_t)B * 4);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
+// ---- evaluation at given points (kernel: nmpc_eval.hip)
+struct EvalArgs {
+  const double *x, *p, *lam_g, *lam_x, *lbx, *ubx, *lbg, *ubg;
+  int64_t ld_x, ld_p, ld_lam_g, ld_lam_x, ld_lbx, ld_ubx, ld_lbg, ld_ubg;
+  double *f, *g, *X, *grad_f, *grad_l, *kkt;
+};
+// the argument checks of both entry points: nothing here touches the device
+static int eval_check(const nmpc_handle* h, int32_t B, const EvalArgs& a) {
+  if (!h) return fail(NMPC_E_INVALID, "null handle");
+  if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
+  if (!a.x || !a.p) return fail(NMPC_E_INVALID, "required pointer is null (x, p)");
+  if (!a.f && !a.g && !a.X && !a.grad_f && !a.grad_l && !a.kkt)
+    return fail(NMPC_E_INVALID, "every output pointer is null");
+  if (a.kkt && (!a.lbx || !a.ubx || !a.lbg || !a.ubg))
+    return fail(NMPC_E_INVALID, "kkt_out needs lbx, ubx, lbg and ubg");
+  const Params& P = h->hp;
+  auto bad = [](const double* q, int64_t ld, int n) { return q && ld != 0 && ld < n; };
+  if (bad(a.x, a.ld_x, P.nwE) || bad(a.p, a.ld_p, P.npE) || bad(a.lam_g, a.ld_lam_g, P.ng) ||
+      bad(a.lam_x, a.ld_lam_x, P.nwE) || bad(a.lbx, a.ld_lbx, P.nwE) || bad(a.ubx, a.ld_ubx, P.nwE) ||
+      bad(a.lbg, a.ld_lbg, P.ng) || bad(a.ubg, a.ld_ubg, P.ng))
+    return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
+  return NMPC_OK;
+}
+// checked arguments, DEVICE pointers: workspace from the handle (sized like a solve's, grown
+// only when it does not cover B yet), then one launch
+static int eval_enqueue(nmpc_handle* h, int32_t B, const EvalArgs& a, void* stream) {
+  const int per = h->ws_doubles > kEvalWs ? h->ws_doubles : kEvalWs;
+  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
+  EvalIO io;
+  io.x = a.x; io.p = a.p; io.lam_g = a.lam_g; io.lam_x = a.lam_x;
+  io.lbx = a.lbx; io.ubx = a.ubx; io.lbg = a.lbg; io.ubg = a.ubg;
+  io.ld_x = a.ld_x; io.ld_p = a.ld_p; io.ld_lam_g = a.ld_lam_g; io.ld_lam_x = a.ld_lam_x;
+  io.ld_lbx = a.ld_lbx; io.ld_ubx = a.ld_ubx; io.ld_lbg = a.ld_lbg; io.ld_ubg = a.ld_ubg;
+  io.f = a.f; io.g = a.g; io.X = a.X; io.grad_f = a.grad_f; io.grad_l = a.grad_l; io.kkt = a.kkt;
+  io.ws = h->dws;
+  const hipError_t e = (hipError_t)nmpc_eval_launch(h->dprm, (int)B, io, stream);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("evaluation launch: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
+int nmpc_eval_batch_dev(nmpc_handle* h, int32_t B, const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                        const double* lam_g, int64_t ld_lam_g, const double* lam_x, int64_t ld_lam_x,
+                        const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx, const double* lbg,
+                        int64_t ld_lbg, const double* ubg, int64_t ld_ubg, double* f_out, double* g_out,
+                        double* X_out, double* grad_f_out, double* grad_l_out, double* kkt_out, void* stream) {
+  const EvalArgs a{x, p, lam_g, lam_x, lbx, ubx, lbg, ubg, ld_x, ld_p, ld_lam_g, ld_lam_x, ld_lbx, ld_ubx, ld_lbg,
+                   ld_ubg, f_out, g_out, X_out, grad_f_out, grad_l_out, kkt_out};
+  if (int rc = eval_check(h, B, a)) return rc;
+  return eval_enqueue(h, B, a, stream);
+}
+
+int nmpc_eval_batch(nmpc_handle* h, int32_t B, const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                    const double* lam_g, int64_t ld_lam_g, const double* lam_x, int64_t ld_lam_x, const double* lbx,
+                    int64_t ld_lbx, const double* ubx, int64_t ld_ubx, const double* lbg, int64_t ld_lbg,
+                    const double* ubg, int64_t ld_ubg, double* f_out, double* g_out, double* X_out,
+                    double* grad_f_out, double* grad_l_out, double* kkt_out) {
+  const EvalArgs a{x, p, lam_g, lam_x, lbx, ubx, lbg, ubg, ld_x, ld_p, ld_lam_g, ld_lam_x, ld_lbx, ld_ubx, ld_lbg,
+                   ld_ubg, f_out, g_out, X_out, grad_f_out, grad_l_out, kkt_out};
+  if (int rc = eval_check(h, B, a)) return rc;
+  const Params& P = h->hp;
+  const size_t nw = P.nwE, ng = P.ng, np = P.npE, nX = (size_t)P.nxE * (P.N + 1);
+  // staging: the eight inputs (absent ones take no room), then the six outputs
+  const double* src[8] = {x, p, lam_g, lam_x, lbx, ubx, lbg, ubg};
+  const int64_t ld[8] = {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_lbx, ld_ubx, ld_lbg, ld_ubg};
+  const size_t vlen[8] = {nw, np, ng, nw, nw, nw, ng, ng};
+  double* hout[6] = {f_out, g_out, X_out, grad_f_out, grad_l_out, kkt_out};
+  const size_t olen[6] = {1, ng, nX, nw, nw, 5};
+  size_t n_in[8], total = 0;
+  for (int i = 0; i < 8; ++i) {
+    n_in[i] = !src[i] ? 0 : (ld[i] == 0 ? vlen[i] : (size_t)(B - 1) * (size_t)ld[i] + vlen[i]);
+    total += n_in[i];
+  }
+  for (int i = 0; i < 6; ++i) total += hout[i] ? (size_t)B * olen[i] : 0;
+  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
+  double* q = h->dbuf;
+  const double* din[8];
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 8; ++i) {
+    din[i] = src[i] ? q : nullptr;
+    if (src[i] && e == hipSuccess) e = hipMemcpy(q, src[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
+    q += n_in[i];
+  }
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
+  double* dout[6];
+  for (int i = 0; i < 6; ++i) {
+    dout[i] = hout[i] ? q : nullptr;
+    q += hout[i] ? (size_t)B * olen[i] : 0;
+  }
+  const EvalArgs d{din[0], din[1], din[2], din[3], din[4], din[5], din[6], din[7], ld_x, ld_p, ld_lam_g, ld_lam_x,
+                   ld_lbx, ld_ubx, ld_lbg, ld_ubg, dout[0], dout[1], dout[2], dout[3], dout[4], dout[5]};
+  if (int rc = eval_enqueue(h, B, d, nullptr)) return rc;
+  e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
+  for (int i = 0; i < 6; ++i)
+    if (hout[i] && e == hipSuccess)
+      e = hipMemcpy(hout[i], dout[i], (size_t)B * olen[i] * sizeof(double), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
   return NMPC_OK;
 }

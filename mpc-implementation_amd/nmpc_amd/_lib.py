@@ -26,6 +26,7 @@ EXPORTS = (
     "nmpc_solve_batch", "nmpc_solve_batch_dev", "nmpc_set_trace", "nmpc_read_trace",
     "nmpc_shift_dev", "nmpc_closed_loop_dev", "nmpc_closed_loop_info", "nmpc_last_error", "nmpc_kernel_info",
     "nmpc_build_id", "nmpc_closed_loop_times", "nmpc_memory_info", "nmpc_reserve_eq",
+    "nmpc_eval_batch", "nmpc_eval_batch_dev",
 )
 
 _OPT_INT = ("max_iter", "acceptable_iter", "max_soc", "max_soft_resto_iters",
@@ -95,6 +96,9 @@ def lib():
     args = [vp, C.c_int32] + [dp, i64] * 6 + [dp] * 7 + [i32p, i32p]
     L.nmpc_solve_batch.argtypes = args
     L.nmpc_solve_batch_dev.argtypes = [vp, C.c_int32] + [vp, i64] * 6 + [vp] * 7 + [vp, vp, vp]
+    if hasattr(L, "nmpc_eval_batch") or not os.environ.get("NMPC_LIB"):  # (an older diagnostic build may lack them)
+        L.nmpc_eval_batch.argtypes = [vp, C.c_int32] + [dp, i64] * 8 + [dp] * 6
+        L.nmpc_eval_batch_dev.argtypes = [vp, C.c_int32] + [vp, i64] * 8 + [vp] * 6 + [vp]
     L.nmpc_set_trace.argtypes = [vp, C.c_int32]
     L.nmpc_read_trace.argtypes = [vp, C.c_int32, dp]
     L.nmpc_shift_dev.argtypes = [vp, C.c_int32, vp, i64, vp, vp, vp, vp, vp]

@@ -104,6 +104,8 @@ class Solver:
         d.opts = make_options(opts)
         d.w1_pidx, d.w2_pidx = spec.w1_pidx, spec.w2_pidx
         self.max_iter = int(d.opts.max_iter)
+        # IPOPT's unscaled acceptance thresholds, applied by certify()
+        self._cert_tol = (float(d.opts.dual_inf_tol), float(d.opts.constr_viol_tol), float(d.opts.compl_inf_tol))
         h = C.c_void_p()
         _lib.check(L.nmpc_create(C.byref(d), C.byref(h)))
         self._h = h
@@ -232,6 +234,102 @@ class Solver:
         _lib.check(L.nmpc_solve_batch_dev(self._h, B, *ins, op("x"), op("f"), op("g"), op("lam_x"),
                                           op("lam_g"), op("lam_p"), op("X"), op("status"), op("iters"),
                                           C.c_void_p(stream.cuda_stream)))
+
+    # ---- evaluation at given points (nmpc_eval_batch: CasADi's nlp_f / nlp_g / nlp_grad_f)
+    def evaluate(self, x, p, lam_g=None, lam_x=None, lbx=None, ubx=None, lbg=None, ubg=None):
+        """f, g, X, grad_f and grad_l = grad_f + J_g' lam_g + lam_x at the given decision
+        vectors, on the GPU (the reference's ``ff(u, p)``, Python/NMPC_TT.py:368, and the
+        ``nlp_f`` / ``nlp_g`` / ``nlp_grad_f`` of a CasADi nlpsol object).  Arguments as
+        ``__call__``'s: one column or (n,B); one column is shared by the batch.  Multipliers
+        in CasADi's sign convention, absent = zeros.  With any bound given (absent ones are
+        infinite) the result also has ``kkt`` (5,B): rows stat = |grad_l|_inf, gmax =
+        |grad_f|_inf, viol, compl, lmax (unnormalised; see nmpc_eval_batch_dev)."""
+        want_kkt = any(v is not None for v in (lbx, ubx, lbg, ubg))
+        args, B = [], 1
+        for name, v, n, dflt in (("x", x, self.nw, None), ("p", p, self.np, None), ("lam_g", lam_g, self.ng, None),
+                                 ("lam_x", lam_x, self.nw, None), ("lbx", lbx, self.nw, -np.inf),
+                                 ("ubx", ubx, self.nw, np.inf), ("lbg", lbg, self.ng, -np.inf),
+                                 ("ubg", ubg, self.ng, np.inf)):
+            if v is None and (dflt is None or not want_kkt):
+                if name in ("x", "p"):
+                    raise ValueError(f"{name} is required")
+                args.append((None, 0))
+                continue
+            a, ld = self._arg(v, n, dflt, name)
+            if ld:
+                if B not in (1, a.shape[0]):
+                    raise ValueError(f"{name}: batch size {a.shape[0]} does not match {B}")
+                B = a.shape[0]
+            args.append((a, ld))
+        out = {"f": np.empty(B), "g": np.empty((B, self.ng)), "X": np.empty((B, self.nX)),
+               "grad_f": np.empty((B, self.nw)), "grad_l": np.empty((B, self.nw))}
+        if want_kkt:
+            out["kkt"] = np.empty((B, 5))
+        ins = []
+        for a, ld in args:
+            ins += [_dptr(a) if a is not None else None, ld]
+        _lib.check(_lib.lib().nmpc_eval_batch(
+            self._h, B, *ins, _dptr(out["f"]), _dptr(out["g"]), _dptr(out["X"]), _dptr(out["grad_f"]),
+            _dptr(out["grad_l"]), _dptr(out["kkt"]) if want_kkt else None))
+        res = {k: v.T for k, v in out.items() if k != "f"}
+        res["f"] = out["f"].reshape(1, B)
+        return res
+
+    def evaluate_device(self, x, p, out: dict, lam_g=None, lam_x=None, lbx=None, ubx=None, lbg=None, ubg=None,
+                        stream=None):
+        """Device path of :meth:`evaluate`: torch CUDA float64 tensors, scenario-major (B, n)
+        or shared (n,).  ``out`` holds preallocated device tensors, any of f (B,), g (B,ng),
+        X (B,nX), grad_f (B,nw), grad_l (B,nw), kkt (B,5) (kkt needs all four bounds).
+        Enqueued on ``stream`` (default = current); never synchronises the host."""
+        import torch  # plumbing only: device memory and streams
+
+        keys = ("f", "g", "X", "grad_f", "grad_l", "kkt")
+        given = [out[k] for k in keys if out.get(k) is not None]
+        if not given:
+            raise ValueError("evaluate_device: out holds none of " + ", ".join(keys))
+        B = given[0].shape[0]
+
+        def dv(t, n):
+            if t is None:
+                return C.c_void_p(0), 0
+            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous()
+            if t.dim() == 1:
+                assert t.shape[0] == n
+                return C.c_void_p(t.data_ptr()), 0
+            assert t.shape == (B, n), (tuple(t.shape), (B, n))
+            return C.c_void_p(t.data_ptr()), n
+
+        ins = []
+        for t, n in ((x, self.nw), (p, self.np), (lam_g, self.ng), (lam_x, self.nw), (lbx, self.nw), (ubx, self.nw),
+                     (lbg, self.ng), (ubg, self.ng)):
+            ins += list(dv(t, n))
+        outs = []
+        for k, shp in zip(keys, ((B,), (B, self.ng), (B, self.nX), (B, self.nw), (B, self.nw), (B, 5))):
+            t = out.get(k)
+            if t is not None:
+                assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp, k
+            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        _lib.check(_lib.lib().nmpc_eval_batch_dev(self._h, B, *ins, *outs, C.c_void_p(stream.cuda_stream)))
+
+    def certify(self, sol: dict, lbx, ubx, lbg, ubg, p):
+        """First-order certificate of a result of ``__call__`` that does not come from the
+        solver: ``sol['x']``, ``sol['lam_g']``, ``sol['lam_x']`` are re-evaluated on the GPU
+        (:meth:`evaluate`) and judged by IPOPT's unscaled acceptance thresholds of this
+        solver's options, read on g(x): per scenario
+        ``stat`` = |grad f + J' lam_g + lam_x|_inf, ``stat_rel`` = stat / (1 + |grad f|_inf),
+        ``viol`` = the largest bound violation, ``compl`` = max |lam| * gap / (1 + |lam|_inf), and
+        ``ok`` = stat <= dual_inf_tol and stat_rel <= 1e-4 and viol <= constr_viol_tol and
+        compl <= compl_inf_tol.  ``kkt`` is the raw (5,B) array.  A NaN anywhere gives ok = False."""
+        ev = self.evaluate(sol["x"], p, lam_g=sol["lam_g"], lam_x=sol["lam_x"], lbx=lbx, ubx=ubx, lbg=lbg, ubg=ubg)
+        stat, gmax, viol, cpl, lmax = ev["kkt"]
+        dual_tol, viol_tol, compl_tol = self._cert_tol
+        with np.errstate(invalid="ignore"):
+            ok = ((stat <= dual_tol) & (stat <= 1e-4 * (1 + gmax)) & (viol <= viol_tol)
+                  & (cpl <= compl_tol * (1 + lmax)))
+        return {"stat": stat, "stat_rel": stat / (1 + gmax), "viol": viol, "compl": cpl / (1 + lmax), "ok": ok,
+                "kkt": ev["kkt"]}
 
     def shift_device(self, p, u_sol, w_out, v_t, w_t, stream=None):
         """Closed-loop shift on device (Python/NMPC_TT.py:13-30), see nmpc_shift_dev."""
