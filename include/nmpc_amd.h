@@ -235,6 +235,42 @@ int nmpc_eval_batch(nmpc_handle* h, int32_t B,
                     double* f_out, double* g_out, double* X_out,
                     double* grad_f_out, double* grad_l_out, double* kkt_out);
 
+/* Jacobian- and Hessian-vector products at GIVEN decision vectors, for a whole batch: the
+ * second-order half of the function layer (CasADi's nlp_jac_g and nlp_hess_l applied to
+ * vectors).  For each of B scenarios and each of nv >= 1 directions v_d in decision space
+ * (nw long, the model's own layout):
+ *   jv_out (ng nv x B) = J_g(x, p) v_d
+ *   hv_out (nw nv x B) = (obj_factor grad^2_w f + sum_i lam_g_i grad^2_w g_i) v_d
+ *                        (CasADi's hess_l convention; lam_g in CasADi's sign convention as in
+ *                        nmpc_eval_batch, NULL = zeros; obj_factor is shared by the batch)
+ *   dX_out (nx(N+1) nv x B) = (dX/dw) v_d, the tangent of the rollout in X_out's layout;
+ *                        stage 0 is exactly 0.
+ * Within a scenario direction d occupies [d n, (d+1) n) of each array.  v is nw nv per
+ * scenario; ld_v = 0 shares one set of directions with every scenario (ld_v = 0 and v = I give
+ * the dense J_g and Hessian).  x, p and lam_g follow nmpc_eval_batch_dev's leading-dimension
+ * rules.  Every output may be NULL, at least one must not be.  No bounds, options, classes or
+ * statuses are involved.  Non-finite input gives non-finite output only in the directions and
+ * scenarios it touches: directions are independent of each other.  Stage 0 is constant in w,
+ * so its terms are structurally absent (with N = 1 only the last stage's row curvature
+ * contributes to the Hessian).
+ * DEVICE pointers, enqueued on `stream`; never synchronises, and allocates nothing once the
+ * handle's workspace covers B (a solve's workspace does).
+ * A NULL handle, B <= 0, nv <= 0, a NULL x, p or v, every output NULL, or a leading dimension
+ * that is neither 0 nor >= the vector length (nw nv for v) return NMPC_E_INVALID before any
+ * device call. */
+int nmpc_products_batch_dev(nmpc_handle* h, int32_t B, int32_t nv,
+                            const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                            const double* lam_g, int64_t ld_lam_g, double obj_factor,
+                            const double* v, int64_t ld_v,
+                            double* jv_out, double* hv_out, double* dX_out, void* stream);
+
+/* Same with HOST pointers; synchronous (staged through the handle's device buffer). */
+int nmpc_products_batch(nmpc_handle* h, int32_t B, int32_t nv,
+                        const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                        const double* lam_g, int64_t ld_lam_g, double obj_factor,
+                        const double* v, int64_t ld_v,
+                        double* jv_out, double* hv_out, double* dX_out);
+
 /* Optional per-iteration trace (debugging / parity): when enabled, the next
  * solve records NMPC_TRACE_FIELDS doubles per iteration per scenario into a
  * device buffer readable with nmpc_read_trace (host pointer,

@@ -29,10 +29,45 @@ constexpr int kEvalTc = kEvalGl + 8 * kEvalStages;
 constexpr int kEvalDc = kEvalTc + 12 * kEvalStages;
 constexpr int kEvalWs = kEvalDc + (5 + NMPC_MAX_OBS) * kEvalStages;
 
+// DEVICE pointers, layouts and leading dimensions as nmpc_products_batch_dev
+// (include/nmpc_amd.h); x, p and v are required, lam_g and every output may be null
+struct ProdIO {
+  const double *x, *p, *lam_g, *v;
+  long long ld_x, ld_p, ld_lam_g, ld_v;
+  double obj_factor;
+  int nv;
+  double *jv, *hv, *dX;
+  double* ws;  // B x chunks x kProdWs doubles of the handle's workspace
+};
+
+// Per-wavefront workspace of the products kernel (nmpc_products.hip): the evaluation's
+// slices plus the stage-cost Hessians (21 per stage).  The stage-cost gradients' slice is
+// reused per direction for h_k = Hxx_k dX_k + Hxu_k du_k once the dynamics multipliers are
+// formed.  A scenario's directions may be dealt to several wavefronts (chunks), each with a
+// slice of its own; every solver class's workspace holds at least one (static_assert in
+// nmpc_products.hip), and the host never picks more chunks than the class's workspace covers.
+constexpr int kProdU = 0;
+constexpr int kProdGl = kProdU + 6 * kEvalStages;
+constexpr int kProdHl = kProdGl + 8 * kEvalStages;
+constexpr int kProdTc = kProdHl + 21 * kEvalStages;
+constexpr int kProdDc = kProdTc + 12 * kEvalStages;
+constexpr int kProdWs = kProdDc + (5 + NMPC_MAX_OBS) * kEvalStages;
+constexpr int kProdMaxChunks = 16;
+// wavefronts a launch is brought up to by chunking: one per SIMD of the MI355X's 256 CUs.
+// Measured with 8 directions at the config-3 shape: B = 256 gains 1.7x from 4
+// wavefronts per scenario, B = 1,024 and 4,096 lose 10 to 30 % with more than one.
+constexpr long long kProdFillWaves = 1024;
+
 }  // namespace nmpc_impl
 
 // Enqueues the evaluation of B scenarios on `stream` (one wavefront per scenario); returns
 // the hipError_t of the launch.  No allocation, no synchronisation.
 int nmpc_eval_launch(const nmpc_impl::Params* dprm, int B, const nmpc_impl::EvalIO& io, void* stream);
+
+// Enqueues the Jacobian- / Hessian-vector products of B scenarios on `stream`: B x chunks
+// wavefronts, wavefront (b, c) forming scenario b's directions c, c + chunks, ...  Same
+// contract as nmpc_eval_launch.
+int nmpc_products_launch(const nmpc_impl::Params* dprm, int B, int chunks, const nmpc_impl::ProdIO& io,
+                         void* stream);
 
 #endif  // NMPC_EVAL_H

@@ -201,3 +201,6 @@ int nmpc_eval_launch(const Params* dprm, int B, const EvalIO& io, void* stream) 
   hipLaunchKernelGGL(nmpc_eval_kernel, dim3(B), dim3(WAVE), 0, (hipStream_t)stream, dprm, B, io);
   return (int)hipGetLastError();
 }
+
+// the Jacobian- and Hessian-vector products at given points: a second kernel of this unit
+#include "nmpc_products.hip"

@@ -5742,6 +5742,108 @@ int nmpc_eval_batch(nmpc_handle* h, int32_t B, const double* x, int64_t ld_x, co
   return NMPC_OK;
 }
 
+// ---- Jacobian- and Hessian-vector products at given points (kernel: nmpc_products.hip)
+struct ProdArgs {
+  const double *x, *p, *lam_g, *v;
+  int64_t ld_x, ld_p, ld_lam_g, ld_v;
+  double obj_factor;
+  double *jv, *hv, *dX;
+};
+// the argument checks of both entry points: nothing here touches the device
+static int prod_check(const nmpc_handle* h, int32_t B, int32_t nv, const ProdArgs& a) {
+  if (!h) return fail(NMPC_E_INVALID, "null handle");
+  if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
+  if (nv <= 0) return fail(NMPC_E_INVALID, "nv <= 0");
+  if (!a.x || !a.p || !a.v) return fail(NMPC_E_INVALID, "required pointer is null (x, p, v)");
+  if (!a.jv && !a.hv && !a.dX) return fail(NMPC_E_INVALID, "every output pointer is null");
+  const Params& P = h->hp;
+  auto bad = [](const double* q, int64_t ld, int64_t n) { return q && ld != 0 && ld < n; };
+  if (bad(a.x, a.ld_x, P.nwE) || bad(a.p, a.ld_p, P.npE) || bad(a.lam_g, a.ld_lam_g, P.ng) ||
+      bad(a.v, a.ld_v, (int64_t)P.nwE * nv))
+    return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
+  return NMPC_OK;
+}
+// checked arguments, DEVICE pointers: workspace from the handle (sized like a solve's, grown
+// only when it does not cover B yet), then one launch.  A scenario's directions are dealt to
+// as many wavefronts as the class's per-scenario workspace holds slices for.
+static int prod_enqueue(nmpc_handle* h, int32_t B, int32_t nv, const ProdArgs& a, void* stream) {
+  const int per = h->ws_doubles > kProdWs ? h->ws_doubles : kProdWs;
+  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
+  int cap = per / kProdWs;
+  if (cap > kProdMaxChunks) cap = kProdMaxChunks;
+  if (cap > nv) cap = nv;
+  // every chunk repeats the scenario's set-up (rollout, derivatives, multipliers), so a batch
+  // that fills the device on its own gets one wavefront per scenario, and a small one as
+  // many as bring it to kProdFillWaves (results do not depend on the choice)
+  int chunks = (int)((kProdFillWaves + B - 1) / B);
+  if (const char* e = std::getenv("NMPC_PRODUCTS_CHUNKS")) chunks = std::atoi(e);  // diagnostics
+  if (chunks > cap) chunks = cap;
+  if (chunks < 1) chunks = 1;
+  ProdIO io;
+  io.x = a.x; io.p = a.p; io.lam_g = a.lam_g; io.v = a.v;
+  io.ld_x = a.ld_x; io.ld_p = a.ld_p; io.ld_lam_g = a.ld_lam_g; io.ld_v = a.ld_v;
+  io.obj_factor = a.obj_factor; io.nv = nv;
+  io.jv = a.jv; io.hv = a.hv; io.dX = a.dX;
+  io.ws = h->dws;
+  const hipError_t e = (hipError_t)nmpc_products_launch(h->dprm, (int)B, chunks, io, stream);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("products launch: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
+int nmpc_products_batch_dev(nmpc_handle* h, int32_t B, int32_t nv, const double* x, int64_t ld_x, const double* p,
+                            int64_t ld_p, const double* lam_g, int64_t ld_lam_g, double obj_factor,
+                            const double* v, int64_t ld_v, double* jv_out, double* hv_out, double* dX_out,
+                            void* stream) {
+  const ProdArgs a{x, p, lam_g, v, ld_x, ld_p, ld_lam_g, ld_v, obj_factor, jv_out, hv_out, dX_out};
+  if (int rc = prod_check(h, B, nv, a)) return rc;
+  return prod_enqueue(h, B, nv, a, stream);
+}
+
+int nmpc_products_batch(nmpc_handle* h, int32_t B, int32_t nv, const double* x, int64_t ld_x, const double* p,
+                        int64_t ld_p, const double* lam_g, int64_t ld_lam_g, double obj_factor, const double* v,
+                        int64_t ld_v, double* jv_out, double* hv_out, double* dX_out) {
+  const ProdArgs a{x, p, lam_g, v, ld_x, ld_p, ld_lam_g, ld_v, obj_factor, jv_out, hv_out, dX_out};
+  if (int rc = prod_check(h, B, nv, a)) return rc;
+  const Params& P = h->hp;
+  const size_t nw = P.nwE, ng = P.ng, np = P.npE, nX = (size_t)P.nxE * (P.N + 1);
+  // staging: the four inputs (an absent lam_g takes no room), then the three outputs
+  const double* src[4] = {x, p, lam_g, v};
+  const int64_t ld[4] = {ld_x, ld_p, ld_lam_g, ld_v};
+  const size_t vlen[4] = {nw, np, ng, nw * (size_t)nv};
+  double* hout[3] = {jv_out, hv_out, dX_out};
+  const size_t olen[3] = {ng * (size_t)nv, nw * (size_t)nv, nX * (size_t)nv};
+  size_t n_in[4], total = 0;
+  for (int i = 0; i < 4; ++i) {
+    n_in[i] = !src[i] ? 0 : (ld[i] == 0 ? vlen[i] : (size_t)(B - 1) * (size_t)ld[i] + vlen[i]);
+    total += n_in[i];
+  }
+  for (int i = 0; i < 3; ++i) total += hout[i] ? (size_t)B * olen[i] : 0;
+  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
+  double* q = h->dbuf;
+  const double* din[4];
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 4; ++i) {
+    din[i] = src[i] ? q : nullptr;
+    if (src[i] && e == hipSuccess) e = hipMemcpy(q, src[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
+    q += n_in[i];
+  }
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
+  double* dout[3];
+  for (int i = 0; i < 3; ++i) {
+    dout[i] = hout[i] ? q : nullptr;
+    q += hout[i] ? (size_t)B * olen[i] : 0;
+  }
+  const ProdArgs d{din[0], din[1], din[2], din[3], ld_x, ld_p, ld_lam_g, ld_v, obj_factor, dout[0], dout[1], dout[2]};
+  if (int rc = prod_enqueue(h, B, nv, d, nullptr)) return rc;
+  e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
+  for (int i = 0; i < 3; ++i)
+    if (hout[i] && e == hipSuccess)
+      e = hipMemcpy(hout[i], dout[i], (size_t)B * olen[i] * sizeof(double), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
 int nmpc_shift_dev(nmpc_handle* h, int32_t B, double* p, int64_t ld_p, const double* u_sol, double* w_out,
                    const double* v_t, const double* w_t, void* stream) {
   if (!h) return fail(NMPC_E_INVALID, "null handle");

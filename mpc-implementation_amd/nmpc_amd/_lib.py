@@ -26,7 +26,7 @@ EXPORTS = (
     "nmpc_solve_batch", "nmpc_solve_batch_dev", "nmpc_set_trace", "nmpc_read_trace",
     "nmpc_shift_dev", "nmpc_closed_loop_dev", "nmpc_closed_loop_info", "nmpc_last_error", "nmpc_kernel_info",
     "nmpc_build_id", "nmpc_closed_loop_times", "nmpc_memory_info", "nmpc_reserve_eq",
-    "nmpc_eval_batch", "nmpc_eval_batch_dev",
+    "nmpc_eval_batch", "nmpc_eval_batch_dev", "nmpc_products_batch", "nmpc_products_batch_dev",
 )
 
 _OPT_INT = ("max_iter", "acceptable_iter", "max_soc", "max_soft_resto_iters",
@@ -99,6 +99,11 @@ def lib():
     if hasattr(L, "nmpc_eval_batch") or not os.environ.get("NMPC_LIB"):  # (an older diagnostic build may lack them)
         L.nmpc_eval_batch.argtypes = [vp, C.c_int32] + [dp, i64] * 8 + [dp] * 6
         L.nmpc_eval_batch_dev.argtypes = [vp, C.c_int32] + [vp, i64] * 8 + [vp] * 6 + [vp]
+    if hasattr(L, "nmpc_products_batch") or not os.environ.get("NMPC_LIB"):
+        L.nmpc_products_batch.argtypes = ([vp, C.c_int32, C.c_int32] + [dp, i64] * 3 + [C.c_double] + [dp, i64]
+                                          + [dp] * 3)
+        L.nmpc_products_batch_dev.argtypes = ([vp, C.c_int32, C.c_int32] + [vp, i64] * 3 + [C.c_double] + [vp, i64]
+                                              + [vp] * 3 + [vp])
     L.nmpc_set_trace.argtypes = [vp, C.c_int32]
     L.nmpc_read_trace.argtypes = [vp, C.c_int32, dp]
     L.nmpc_shift_dev.argtypes = [vp, C.c_int32, vp, i64, vp, vp, vp, vp, vp]

@@ -331,6 +331,110 @@ class Solver:
         return {"stat": stat, "stat_rel": stat / (1 + gmax), "viol": viol, "compl": cpl / (1 + lmax), "ok": ok,
                 "kkt": ev["kkt"]}
 
+    # ---- products at given points (nmpc_products_batch: CasADi's nlp_jac_g / nlp_hess_l on vectors)
+    def _products(self, x, p, v, ld_v, nv, lam_g, obj_factor, want=("jv", "hv", "dX")):
+        """v: (1 or B, nv, nw) C-contiguous, ld_v 0 or nw * nv.  Returns (B, nv, n) arrays."""
+        args, B = [], 1
+        for name, a, n in (("x", x, self.nw), ("p", p, self.np), ("lam_g", lam_g, self.ng)):
+            if a is None:
+                if name != "lam_g":
+                    raise ValueError(f"{name} is required")
+                args.append((None, 0))
+                continue
+            a, ld = self._arg(a, n, 0.0, name)
+            if ld:
+                if B not in (1, a.shape[0]):
+                    raise ValueError(f"{name}: batch size {a.shape[0]} does not match {B}")
+                B = a.shape[0]
+            args.append((a, ld))
+        if ld_v:
+            if B not in (1, v.shape[0]):
+                raise ValueError(f"v: batch size {v.shape[0]} does not match {B}")
+            B = v.shape[0]
+        sizes = {"jv": self.ng, "hv": self.nw, "dX": self.nX}
+        out = {k: np.empty((B, nv, sizes[k])) for k in want}
+        ins = []
+        for a, ld in args:
+            ins += [_dptr(a) if a is not None else None, ld]
+        _lib.check(_lib.lib().nmpc_products_batch(
+            self._h, B, nv, *ins, float(obj_factor), _dptr(v), ld_v,
+            *[_dptr(out[k]) if k in out else None for k in ("jv", "hv", "dX")]))
+        return out
+
+    def products(self, x, p, v, lam_g=None, obj_factor=1.0):
+        """Jacobian- and Hessian-vector products at the given decision vectors, on the GPU:
+        ``jv`` (ng,nv,B) = J_g v, ``hv`` (nw,nv,B) = (obj_factor grad^2 f + sum lam_g_i grad^2 g_i) v
+        (CasADi's ``hess_l`` convention, lam_g absent = zeros) and ``dX`` (nX,nv,B) = (dX/dw) v,
+        the tangent of the rollout.  x, p, lam_g as :meth:`evaluate`'s; ``v`` is one direction
+        (nw,), directions (nw,nv) shared by the batch, or (nw,nv,B)."""
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 1:
+            a = a.reshape(-1, 1)
+        if a.ndim not in (2, 3) or a.shape[0] != self.nw or a.shape[1] < 1:
+            raise ValueError(f"v: expected ({self.nw},), ({self.nw},nv) or ({self.nw},nv,B), got shape {a.shape}")
+        nv = a.shape[1]
+        if a.ndim == 2:
+            vv, ld_v = np.ascontiguousarray(a.T).reshape(1, nv, self.nw), 0
+        else:
+            vv, ld_v = np.ascontiguousarray(a.transpose(2, 1, 0)), self.nw * nv
+        out = self._products(x, p, vv, ld_v, nv, lam_g, obj_factor)
+        return {k: np.ascontiguousarray(t.transpose(2, 1, 0)) for k, t in out.items()}
+
+    def products_device(self, x, p, v, out: dict, lam_g=None, obj_factor=1.0, stream=None):
+        """Device path of :meth:`products`: torch CUDA float64 tensors, x, p, lam_g
+        scenario-major (B, n) or shared (n,); ``v`` is (B, nv, nw) or shared (nv, nw); ``out``
+        holds preallocated device tensors, any of jv (B,nv,ng), hv (B,nv,nw), dX (B,nv,nX).
+        Enqueued on ``stream`` (default = current); never synchronises the host."""
+        import torch  # plumbing only: device memory and streams
+
+        keys = ("jv", "hv", "dX")
+        given = [out[k] for k in keys if out.get(k) is not None]
+        if not given:
+            raise ValueError("products_device: out holds none of " + ", ".join(keys))
+        B, nv = given[0].shape[0], given[0].shape[1]
+
+        def dv(t, n):
+            if t is None:
+                return C.c_void_p(0), 0
+            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous()
+            if t.dim() == 1:
+                assert t.shape[0] == n
+                return C.c_void_p(t.data_ptr()), 0
+            assert t.shape == (B, n), (tuple(t.shape), (B, n))
+            return C.c_void_p(t.data_ptr()), n
+
+        ins = []
+        for t, n in ((x, self.nw), (p, self.np), (lam_g, self.ng)):
+            ins += list(dv(t, n))
+        assert v.dtype == torch.float64 and v.is_cuda and v.is_contiguous()
+        assert tuple(v.shape) in ((nv, self.nw), (B, nv, self.nw)), tuple(v.shape)
+        ld_v = 0 if v.dim() == 2 else nv * self.nw
+        outs = []
+        for k, n in zip(keys, (self.ng, self.nw, self.nX)):
+            t = out.get(k)
+            if t is not None:
+                assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B, nv, n), k
+            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        _lib.check(_lib.lib().nmpc_products_batch_dev(self._h, B, nv, *ins, float(obj_factor),
+                                                      C.c_void_p(v.data_ptr()), ld_v, *outs,
+                                                      C.c_void_p(stream.cuda_stream)))
+
+    def jacobian(self, x, p):
+        """Dense J_g (ng,nw,B) at the given decision vectors (CasADi's ``nlp_jac_g``): the
+        identity directions, shared by the batch, through :meth:`products`' kernel."""
+        eye = np.eye(self.nw).reshape(1, self.nw, self.nw)
+        out = self._products(x, p, eye, 0, self.nw, None, 1.0, want=("jv",))
+        return np.ascontiguousarray(out["jv"].transpose(2, 1, 0))
+
+    def hessian(self, x, p, lam_g=None, obj_factor=1.0):
+        """Dense Hessian of the Lagrangian (nw,nw,B), obj_factor grad^2 f + sum lam_g_i grad^2 g_i
+        (CasADi's ``nlp_hess_l``, the full symmetric matrix), column d being W e_d."""
+        eye = np.eye(self.nw).reshape(1, self.nw, self.nw)
+        out = self._products(x, p, eye, 0, self.nw, lam_g, obj_factor, want=("hv",))
+        return np.ascontiguousarray(out["hv"].transpose(2, 1, 0))
+
     def shift_device(self, p, u_sol, w_out, v_t, w_t, stream=None):
         """Closed-loop shift on device (Python/NMPC_TT.py:13-30), see nmpc_shift_dev."""
         import torch
