@@ -271,6 +271,63 @@ int nmpc_products_batch(nmpc_handle* h, int32_t B, int32_t nv,
                         const double* v, int64_t ld_v,
                         double* jv_out, double* hv_out, double* dX_out);
 
+/* Solves with the condensed KKT matrix at GIVEN decision vectors, for a whole batch: the
+ * Newton-step operator of the interior-point method (the solver's Riccati factorisation, its
+ * solves and its inertia verdict) as a function of its own.  For each of B scenarios, at x
+ * with parameters p, multipliers lam_g (CasADi's sign convention, NULL = zeros) and
+ * obj_factor (shared by the batch),
+ *   M  = W + diag(sigma_x) + delta I + J^T diag(sigma_s + delta) J
+ *   W  = obj_factor grad^2_w f + sum_i lam_g_i grad^2_w g_i      (nmpc_products_batch's hv)
+ *   M dw_d = r_w,d + J^T r_g,d                                   for each of nr >= 1 right-hand sides
+ * i.e. IPOPT's primal-dual system with the slacks and bound multipliers eliminated; delta is
+ * the primal regularisation delta_w, which enters the slack block too.  M is unscaled (unit
+ * row scaling, objective factor = obj_factor).
+ *   sigma_x (nw x B), NULL = zeros: the variables' barrier weights.  +inf marks a fixed
+ *     variable: its row and column leave the system and dw is exactly 0 there.
+ *   sigma_s (ng x B), NULL = zeros: the rows' (slacks') barrier weights, finite.
+ *   delta (B), NULL = 0; ld_delta = 0 shares one value.
+ *   r_w (nw nr per scenario), r_g (ng nr per scenario): either may be NULL (= zeros), not both;
+ *     right-hand side d occupies [d n, (d+1) n).  A leading dimension of 0 shares one set with
+ *     every scenario, as for sigma_x and sigma_s.
+ * x, p and lam_g follow nmpc_products_batch_dev's leading-dimension rules.
+ *   dw_out  (nw nr x B)        = dw_d
+ *   dX_out  (nx(N+1) nr x B)   = (dX/dw) dw_d, the state step; stage 0 is exactly 0
+ *   jdw_out (ng nr x B)        = J dw_d (the row step: ds = J dw - r_d, dlam_g = sigma_s ds ...)
+ *   info_out (B x int32): 0 = factorised and every Riccati pivot positive definite (IPOPT's
+ *     inertia test: M is positive definite); 1 = wrong inertia or singular; -11 = invalid
+ *     weights (a negative or NaN sigma_x / sigma_s / delta, an infinite sigma_s or delta).
+ *     With 1 or -11 that scenario's other outputs are NaN, never a step from a failed factor.
+ * Each output may be NULL, at least one of dw_out, dX_out, jdw_out must not be.  Stage 0's
+ * rows have a zero Jacobian: their sigma_s and r_g entries are never read.  The right-hand
+ * sides are independent: a non-finite one gives a non-finite column of its own only.  The
+ * no-gimbal model's absent controls are not part of the system (nw = 3N).  An infinite
+ * sigma_s (an equality row) is not supported here.
+ * DEVICE pointers, enqueued on `stream`; never synchronises, and allocates nothing once the
+ * handle's workspace covers B (a solve's workspace does).  One wavefront per scenario forms
+ * every right-hand side: the factorisation is done once.
+ * A NULL handle, B <= 0, nr <= 0, a NULL x or p, both right-hand sides NULL, dw_out, dX_out
+ * and jdw_out all NULL, or a leading dimension that is neither 0 nor >= the vector length
+ * return NMPC_E_INVALID before any device call. */
+int nmpc_kkt_solve_batch_dev(nmpc_handle* h, int32_t B, int32_t nr,
+                             const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                             const double* lam_g, int64_t ld_lam_g, double obj_factor,
+                             const double* sigma_x, int64_t ld_sigma_x,
+                             const double* sigma_s, int64_t ld_sigma_s,
+                             const double* delta, int64_t ld_delta,
+                             const double* r_w, int64_t ld_r_w, const double* r_g, int64_t ld_r_g,
+                             double* dw_out, double* dX_out, double* jdw_out, int32_t* info_out,
+                             void* stream);
+
+/* Same with HOST pointers; synchronous (staged through the handle's device buffer). */
+int nmpc_kkt_solve_batch(nmpc_handle* h, int32_t B, int32_t nr,
+                         const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                         const double* lam_g, int64_t ld_lam_g, double obj_factor,
+                         const double* sigma_x, int64_t ld_sigma_x,
+                         const double* sigma_s, int64_t ld_sigma_s,
+                         const double* delta, int64_t ld_delta,
+                         const double* r_w, int64_t ld_r_w, const double* r_g, int64_t ld_r_g,
+                         double* dw_out, double* dX_out, double* jdw_out, int32_t* info_out);
+
 /* Optional per-iteration trace (debugging / parity): when enabled, the next
  * solve records NMPC_TRACE_FIELDS doubles per iteration per scenario into a
  * device buffer readable with nmpc_read_trace (host pointer,

@@ -58,7 +58,44 @@ constexpr int kProdMaxChunks = 16;
 // wavefronts per scenario, B = 1,024 and 4,096 lose 10 to 30 % with more than one.
 constexpr long long kProdFillWaves = 1024;
 
+// DEVICE pointers, layouts and leading dimensions as nmpc_kkt_solve_batch_dev
+// (include/nmpc_amd.h); x and p are required, one of r_w / r_g and one of dw / dX / jdw
+struct KktIO {
+  const double *x, *p, *lam_g, *sigma_x, *sigma_s, *delta, *r_w, *r_g;
+  long long ld_x, ld_p, ld_lam_g, ld_sigma_x, ld_sigma_s, ld_delta, ld_r_w, ld_r_g;
+  double obj_factor;
+  int nr;
+  double *dw, *dX, *jdw;
+  int* info;
+  double* ws;  // B x kKktWs doubles of the handle's workspace
+};
+
+// Per-scenario workspace of the KKT kernel (nmpc_kkt.hip): the products kernel's slices, the
+// stage summaries Q_k (36 per stage), the Riccati factors K_k (48), R~_k (21) and k_k (6),
+// sigma_x in the kernel's 6-per-stage layout, and one right-hand side's control terms and
+// step.  Sized for N = NMPC_MAX_N like the slices above; every solver class's workspace is
+// larger (static_assert in nmpc_kkt.hip), so a handle whose workspace covers B for a solve
+// covers B here.
+constexpr int kKktU = 0;
+constexpr int kKktGl = kKktU + 6 * kEvalStages;
+constexpr int kKktHl = kKktGl + 8 * kEvalStages;
+constexpr int kKktTc = kKktHl + 21 * kEvalStages;
+constexpr int kKktDc = kKktTc + 12 * kEvalStages;
+constexpr int kKktQs = kKktDc + (5 + NMPC_MAX_OBS) * kEvalStages;
+constexpr int kKktK = kKktQs + 36 * kEvalStages;
+constexpr int kKktRk = kKktK + 48 * kEvalStages;
+constexpr int kKktKf = kKktRk + 21 * kEvalStages;
+constexpr int kKktRd = kKktKf + 6 * kEvalStages;
+constexpr int kKktRv = kKktRd + 6 * kEvalStages;
+constexpr int kKktDu = kKktRv + 6 * kEvalStages;
+constexpr int kKktWs = kKktDu + 6 * kEvalStages;
+
 }  // namespace nmpc_impl
+
+// Enqueues the KKT solves of B scenarios on `stream` (one wavefront per scenario, every
+// right-hand side on it: another wavefront would repeat the factorisation).  Same contract as
+// nmpc_eval_launch.
+int nmpc_kkt_launch(const nmpc_impl::Params* dprm, int B, const nmpc_impl::KktIO& io, void* stream);
 
 // Enqueues the evaluation of B scenarios on `stream` (one wavefront per scenario); returns
 // the hipError_t of the launch.  No allocation, no synchronisation.

@@ -204,3 +204,6 @@ int nmpc_eval_launch(const Params* dprm, int B, const EvalIO& io, void* stream) 
 
 // the Jacobian- and Hessian-vector products at given points: a second kernel of this unit
 #include "nmpc_products.hip"
+
+// the condensed KKT solves at given points: a third kernel of this unit
+#include "nmpc_kkt.hip"

@@ -5844,6 +5844,112 @@ int nmpc_products_batch(nmpc_handle* h, int32_t B, int32_t nv, const double* x, 
   return NMPC_OK;
 }
 
+// ---- condensed KKT solves at given points (kernel: nmpc_kkt.hip)
+struct KktArgs {
+  const double *x, *p, *lam_g, *sigma_x, *sigma_s, *delta, *r_w, *r_g;
+  int64_t ld_x, ld_p, ld_lam_g, ld_sigma_x, ld_sigma_s, ld_delta, ld_r_w, ld_r_g;
+  double obj_factor;
+  double *dw, *dX, *jdw;
+  int32_t* info;
+};
+// the argument checks of both entry points: nothing here touches the device
+static int kkt_check(const nmpc_handle* h, int32_t B, int32_t nr, const KktArgs& a) {
+  if (!h) return fail(NMPC_E_INVALID, "null handle");
+  if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
+  if (nr <= 0) return fail(NMPC_E_INVALID, "nr <= 0");
+  if (!a.x || !a.p) return fail(NMPC_E_INVALID, "required pointer is null (x, p)");
+  if (!a.r_w && !a.r_g) return fail(NMPC_E_INVALID, "both right-hand sides are null (r_w, r_g)");
+  if (!a.dw && !a.dX && !a.jdw) return fail(NMPC_E_INVALID, "every output pointer is null (dw, dX, jdw)");
+  const Params& P = h->hp;
+  auto bad = [](const double* q, int64_t ld, int64_t n) { return q && ld != 0 && ld < n; };
+  if (bad(a.x, a.ld_x, P.nwE) || bad(a.p, a.ld_p, P.npE) || bad(a.lam_g, a.ld_lam_g, P.ng) ||
+      bad(a.sigma_x, a.ld_sigma_x, P.nwE) || bad(a.sigma_s, a.ld_sigma_s, P.ng) || bad(a.delta, a.ld_delta, 1) ||
+      bad(a.r_w, a.ld_r_w, (int64_t)P.nwE * nr) || bad(a.r_g, a.ld_r_g, (int64_t)P.ng * nr))
+    return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
+  return NMPC_OK;
+}
+// checked arguments, DEVICE pointers: workspace from the handle (sized like a solve's, grown
+// only when it does not cover B yet), then one launch
+static int kkt_enqueue(nmpc_handle* h, int32_t B, int32_t nr, const KktArgs& a, void* stream) {
+  const int per = h->ws_doubles > kKktWs ? h->ws_doubles : kKktWs;
+  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
+  KktIO io;
+  io.x = a.x; io.p = a.p; io.lam_g = a.lam_g; io.sigma_x = a.sigma_x; io.sigma_s = a.sigma_s; io.delta = a.delta;
+  io.r_w = a.r_w; io.r_g = a.r_g;
+  io.ld_x = a.ld_x; io.ld_p = a.ld_p; io.ld_lam_g = a.ld_lam_g; io.ld_sigma_x = a.ld_sigma_x;
+  io.ld_sigma_s = a.ld_sigma_s; io.ld_delta = a.ld_delta; io.ld_r_w = a.ld_r_w; io.ld_r_g = a.ld_r_g;
+  io.obj_factor = a.obj_factor; io.nr = nr;
+  io.dw = a.dw; io.dX = a.dX; io.jdw = a.jdw; io.info = a.info;
+  io.ws = h->dws;
+  const hipError_t e = (hipError_t)nmpc_kkt_launch(h->dprm, (int)B, io, stream);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("KKT solve launch: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
+int nmpc_kkt_solve_batch_dev(nmpc_handle* h, int32_t B, int32_t nr, const double* x, int64_t ld_x, const double* p,
+                             int64_t ld_p, const double* lam_g, int64_t ld_lam_g, double obj_factor,
+                             const double* sigma_x, int64_t ld_sigma_x, const double* sigma_s, int64_t ld_sigma_s,
+                             const double* delta, int64_t ld_delta, const double* r_w, int64_t ld_r_w,
+                             const double* r_g, int64_t ld_r_g, double* dw_out, double* dX_out, double* jdw_out,
+                             int32_t* info_out, void* stream) {
+  const KktArgs a{x, p, lam_g, sigma_x, sigma_s, delta, r_w, r_g, ld_x, ld_p, ld_lam_g, ld_sigma_x, ld_sigma_s,
+                  ld_delta, ld_r_w, ld_r_g, obj_factor, dw_out, dX_out, jdw_out, info_out};
+  if (int rc = kkt_check(h, B, nr, a)) return rc;
+  return kkt_enqueue(h, B, nr, a, stream);
+}
+
+int nmpc_kkt_solve_batch(nmpc_handle* h, int32_t B, int32_t nr, const double* x, int64_t ld_x, const double* p,
+                         int64_t ld_p, const double* lam_g, int64_t ld_lam_g, double obj_factor,
+                         const double* sigma_x, int64_t ld_sigma_x, const double* sigma_s, int64_t ld_sigma_s,
+                         const double* delta, int64_t ld_delta, const double* r_w, int64_t ld_r_w, const double* r_g,
+                         int64_t ld_r_g, double* dw_out, double* dX_out, double* jdw_out, int32_t* info_out) {
+  const KktArgs a{x, p, lam_g, sigma_x, sigma_s, delta, r_w, r_g, ld_x, ld_p, ld_lam_g, ld_sigma_x, ld_sigma_s,
+                  ld_delta, ld_r_w, ld_r_g, obj_factor, dw_out, dX_out, jdw_out, info_out};
+  if (int rc = kkt_check(h, B, nr, a)) return rc;
+  const Params& P = h->hp;
+  const size_t nw = P.nwE, ng = P.ng, np = P.npE, nX = (size_t)P.nxE * (P.N + 1);
+  // staging: the eight inputs (absent ones take no room), the three outputs, then the verdicts
+  const double* src[8] = {x, p, lam_g, sigma_x, sigma_s, delta, r_w, r_g};
+  const int64_t ld[8] = {ld_x, ld_p, ld_lam_g, ld_sigma_x, ld_sigma_s, ld_delta, ld_r_w, ld_r_g};
+  const size_t vlen[8] = {nw, np, ng, nw, ng, 1, nw * (size_t)nr, ng * (size_t)nr};
+  double* hout[3] = {dw_out, dX_out, jdw_out};
+  const size_t olen[3] = {nw * (size_t)nr, nX * (size_t)nr, ng * (size_t)nr};
+  size_t n_in[8], total = 0;
+  for (int i = 0; i < 8; ++i) {
+    n_in[i] = !src[i] ? 0 : (ld[i] == 0 ? vlen[i] : (size_t)(B - 1) * (size_t)ld[i] + vlen[i]);
+    total += n_in[i];
+  }
+  for (int i = 0; i < 3; ++i) total += hout[i] ? (size_t)B * olen[i] : 0;
+  total += info_out ? ((size_t)B + 1) / 2 : 0;  // B int32 in whole doubles
+  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
+  double* q = h->dbuf;
+  const double* din[8];
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 8; ++i) {
+    din[i] = src[i] ? q : nullptr;
+    if (src[i] && e == hipSuccess) e = hipMemcpy(q, src[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
+    q += n_in[i];
+  }
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
+  double* dout[3];
+  for (int i = 0; i < 3; ++i) {
+    dout[i] = hout[i] ? q : nullptr;
+    q += hout[i] ? (size_t)B * olen[i] : 0;
+  }
+  int32_t* dinfo = info_out ? (int32_t*)q : nullptr;
+  const KktArgs d{din[0], din[1], din[2], din[3], din[4], din[5], din[6], din[7], ld_x, ld_p, ld_lam_g,
+                  ld_sigma_x, ld_sigma_s, ld_delta, ld_r_w, ld_r_g, obj_factor, dout[0], dout[1], dout[2], dinfo};
+  if (int rc = kkt_enqueue(h, B, nr, d, nullptr)) return rc;
+  e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
+  for (int i = 0; i < 3; ++i)
+    if (hout[i] && e == hipSuccess)
+      e = hipMemcpy(hout[i], dout[i], (size_t)B * olen[i] * sizeof(double), hipMemcpyDeviceToHost);
+  if (info_out && e == hipSuccess) e = hipMemcpy(info_out, dinfo, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
 int nmpc_shift_dev(nmpc_handle* h, int32_t B, double* p, int64_t ld_p, const double* u_sol, double* w_out,
                    const double* v_t, const double* w_t, void* stream) {
   if (!h) return fail(NMPC_E_INVALID, "null handle");

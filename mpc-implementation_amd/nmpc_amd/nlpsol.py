@@ -106,6 +106,10 @@ class Solver:
         self.max_iter = int(d.opts.max_iter)
         # IPOPT's unscaled acceptance thresholds, applied by certify()
         self._cert_tol = (float(d.opts.dual_inf_tol), float(d.opts.constr_viol_tol), float(d.opts.compl_inf_tol))
+        self._bound_relax = float(d.opts.bound_relax_factor)  # barrier_weights()
+        # IPOPT's inertia-correction ladder, applied by sensitivity()
+        self._perturb = (float(d.opts.first_hessian_perturbation), float(d.opts.perturb_inc_fact_first),
+                         float(d.opts.perturb_inc_fact), float(d.opts.max_hessian_perturbation))
         h = C.c_void_p()
         _lib.check(L.nmpc_create(C.byref(d), C.byref(h)))
         self._h = h
@@ -434,6 +438,231 @@ class Solver:
         eye = np.eye(self.nw).reshape(1, self.nw, self.nw)
         out = self._products(x, p, eye, 0, self.nw, lam_g, obj_factor, want=("hv",))
         return np.ascontiguousarray(out["hv"].transpose(2, 1, 0))
+
+    # ---- condensed KKT solves at given points (nmpc_kkt_solve_batch: the Newton-step operator)
+    def _rhs(self, r, n: int, name: str):
+        """(n,), (n,nr) or (n,nr,B) -> ((1 or B, nr, n) C-contiguous, leading dimension, nr)."""
+        a = np.asarray(r, dtype=np.float64)
+        if a.ndim == 1:
+            a = a.reshape(-1, 1)
+        if a.ndim not in (2, 3) or a.shape[0] != n or a.shape[1] < 1:
+            raise ValueError(f"{name}: expected ({n},), ({n},nr) or ({n},nr,B), got shape {a.shape}")
+        nr = a.shape[1]
+        if a.ndim == 2:
+            return np.ascontiguousarray(a.T).reshape(1, nr, n), 0, nr
+        return np.ascontiguousarray(a.transpose(2, 1, 0)), n * nr, nr
+
+    def kkt_solve(self, x, p, r_w=None, r_g=None, lam_g=None, obj_factor=1.0, sigma_x=None, sigma_s=None,
+                  delta=None):
+        """Solves with the condensed KKT matrix at the given decision vectors, on the GPU:
+        ``M dw = r_w + J' r_g`` with ``M = W + diag(sigma_x) + delta I + J' diag(sigma_s + delta) J``
+        and W the Hessian of :meth:`hessian` (same ``lam_g`` / ``obj_factor``), by the solver's
+        Riccati factorisation.  x, p, lam_g as :meth:`evaluate`'s; ``sigma_x`` (nw,) or (nw,B)
+        and ``sigma_s`` (ng,) or (ng,B) are non-negative weights (absent = zeros; ``+inf`` in
+        sigma_x fixes the variable: its dw is exactly 0); ``delta`` a scalar or (B,).  ``r_w`` /
+        ``r_g`` are one right-hand side (n,), several (n,nr) shared by the batch, or (n,nr,B);
+        one of them may be absent (zeros).  Returns ``dw`` (nw,nr,B), ``dX`` (nX,nr,B) the state
+        step, ``jdw`` (ng,nr,B) = J dw and ``info`` (B,): 0 = factorised with the right inertia
+        (M positive definite), 1 = wrong inertia or singular, -11 = invalid weights; with 1 or
+        -11 the scenario's other outputs are NaN."""
+        if r_w is None and r_g is None:
+            raise ValueError("r_w or r_g is required")
+        args, B = [], 1
+
+        def batch(name, rows):
+            nonlocal B
+            if B not in (1, rows):
+                raise ValueError(f"{name}: batch size {rows} does not match {B}")
+            B = rows
+
+        for name, a, n in (("x", x, self.nw), ("p", p, self.np), ("lam_g", lam_g, self.ng),
+                           ("sigma_x", sigma_x, self.nw), ("sigma_s", sigma_s, self.ng)):
+            if a is None:
+                if name in ("x", "p"):
+                    raise ValueError(f"{name} is required")
+                args.append((None, 0))
+                continue
+            a, ld = self._arg(a, n, 0.0, name)
+            if ld:
+                batch(name, a.shape[0])
+            args.append((a, ld))
+        if delta is None:
+            dl, ld_dl = None, 0
+        else:
+            dl = np.ascontiguousarray(np.asarray(delta, dtype=np.float64).reshape(-1))
+            ld_dl = 0 if dl.shape[0] == 1 else 1
+            if ld_dl:
+                batch("delta", dl.shape[0])
+        nr, rhs = None, []
+        for name, r, n in (("r_w", r_w, self.nw), ("r_g", r_g, self.ng)):
+            if r is None:
+                rhs.append((None, 0))
+                continue
+            a, ld, k = self._rhs(r, n, name)
+            if nr not in (None, k):
+                raise ValueError(f"{name}: {k} right-hand sides do not match {nr}")
+            nr = k
+            if ld:
+                batch(name, a.shape[0])
+            rhs.append((a, ld))
+        out = {"dw": np.empty((B, nr, self.nw)), "dX": np.empty((B, nr, self.nX)), "jdw": np.empty((B, nr, self.ng))}
+        info = np.empty(B, dtype=np.int32)
+        ins = []
+        for a, ld in args[:3]:
+            ins += [_dptr(a) if a is not None else None, ld]
+        ins.append(float(obj_factor))
+        for a, ld in args[3:] + [(dl, ld_dl)] + rhs:
+            ins += [_dptr(a) if a is not None else None, ld]
+        _lib.check(_lib.lib().nmpc_kkt_solve_batch(
+            self._h, B, nr, *ins, _dptr(out["dw"]), _dptr(out["dX"]), _dptr(out["jdw"]), info.ctypes.data_as(_IP)))
+        res = {k: np.ascontiguousarray(t.transpose(2, 1, 0)) for k, t in out.items()}
+        res["info"] = info
+        return res
+
+    def kkt_solve_device(self, x, p, out: dict, r_w=None, r_g=None, lam_g=None, obj_factor=1.0, sigma_x=None,
+                         sigma_s=None, delta=None, stream=None):
+        """Device path of :meth:`kkt_solve`: torch CUDA float64 tensors, x, p, lam_g, sigma_x,
+        sigma_s scenario-major (B, n) or shared (n,); ``delta`` (B,) or shared (1,); ``r_w`` is
+        (B, nr, nw) or shared (nr, nw), ``r_g`` (B, nr, ng) or (nr, ng); ``out`` holds
+        preallocated device tensors, any of dw (B,nr,nw), dX (B,nr,nX), jdw (B,nr,ng) and
+        info (B,) int32 (at least one of the first three).  Enqueued on ``stream`` (default =
+        current); never synchronises the host."""
+        import torch  # plumbing only: device memory and streams
+
+        keys = ("dw", "dX", "jdw")
+        given = [out[k] for k in keys if out.get(k) is not None]
+        if not given:
+            raise ValueError("kkt_solve_device: out holds none of " + ", ".join(keys))
+        if r_w is None and r_g is None:
+            raise ValueError("r_w or r_g is required")
+        B, nr = given[0].shape[0], given[0].shape[1]
+
+        def dv(t, n):
+            if t is None:
+                return C.c_void_p(0), 0
+            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous()
+            if t.dim() == 1:
+                assert t.shape[0] == n
+                return C.c_void_p(t.data_ptr()), 0
+            assert t.shape == (B, n), (tuple(t.shape), (B, n))
+            return C.c_void_p(t.data_ptr()), n
+
+        def rv(t, n, name):
+            if t is None:
+                return C.c_void_p(0), 0
+            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), name
+            assert tuple(t.shape) in ((nr, n), (B, nr, n)), (name, tuple(t.shape))
+            return C.c_void_p(t.data_ptr()), (0 if t.dim() == 2 else nr * n)
+
+        ins = []
+        for t, n in ((x, self.nw), (p, self.np), (lam_g, self.ng)):
+            ins += list(dv(t, n))
+        ins.append(float(obj_factor))
+        for t, n in ((sigma_x, self.nw), (sigma_s, self.ng)):
+            ins += list(dv(t, n))
+        if delta is None:
+            ins += [C.c_void_p(0), 0]
+        else:
+            assert delta.dtype == torch.float64 and delta.is_cuda and delta.is_contiguous()
+            assert tuple(delta.shape) in ((1,), (B,)), tuple(delta.shape)
+            ins += [C.c_void_p(delta.data_ptr()), 0 if delta.shape[0] == 1 else 1]
+        ins += list(rv(r_w, self.nw, "r_w")) + list(rv(r_g, self.ng, "r_g"))
+        outs = []
+        for k, n in zip(keys, (self.nw, self.nX, self.ng)):
+            t = out.get(k)
+            if t is not None:
+                assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B, nr, n), k
+            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
+        t = out.get("info")
+        if t is not None:
+            assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B,), "info"
+        outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        _lib.check(_lib.lib().nmpc_kkt_solve_batch_dev(self._h, B, nr, *ins, *outs, C.c_void_p(stream.cuda_stream)))
+
+    def barrier_weights(self, sol: dict, lbx, ubx, lbg, ubg):
+        """The barrier weights Sigma_x (nw,B) and Sigma_s (ng,B) at a result of ``__call__``,
+        from its signed multipliers (CasADi: negative towards the lower bound):
+        ``sigma = max(-lam, 0) / max(v - lo, eps) + max(lam, 0) / max(hi - v, eps)`` with
+        ``eps = bound_relax_factor * max(1, |bound|)`` of this solver's options (the amount
+        IPOPT moves the bound outwards, so the slack of an active bound is not 0).  A fixed
+        variable (lbx == ubx) gets ``+inf``, which :meth:`kkt_solve` takes as "leaves the
+        system"; an equality row (lbg == ubg) raises: it needs the augmented system."""
+        def weights(v, lam, lo, hi, n, name):
+            v, lam = np.asarray(v, dtype=np.float64).reshape(n, -1), np.asarray(lam, dtype=np.float64).reshape(n, -1)
+            lo = np.asarray(lo, dtype=np.float64).reshape(n, -1) * np.ones_like(v)
+            hi = np.asarray(hi, dtype=np.float64).reshape(n, -1) * np.ones_like(v)
+            brf = self._bound_relax
+            with np.errstate(invalid="ignore"):
+                sl = np.maximum(v - lo, brf * np.maximum(1.0, np.abs(lo)))
+                su = np.maximum(hi - v, brf * np.maximum(1.0, np.abs(hi)))
+                s = np.maximum(-lam, 0.0) / sl + np.maximum(lam, 0.0) / su
+            return s, lo == hi
+
+        sx, fx = weights(sol["x"], sol["lam_x"], lbx, ubx, self.nw, "x")
+        ss, eq = weights(sol["g"], sol["lam_g"], lbg, ubg, self.ng, "g")
+        if np.any(eq):
+            raise ValueError("barrier_weights: equality rows (lbg == ubg) are not supported")
+        sx[fx] = np.inf
+        return sx, ss
+
+    def sensitivity(self, sol: dict, lbx, ubx, lbg, ubg, p, dp, fd_step: float = 1e-3):
+        """First-order change of a solution with the parameters: ``dx`` (nw,nd,B) = dx*/dp dp_d
+        and ``dlam_g`` (ng,nd,B) for the directions ``dp`` (np,), (np,nd) or (np,nd,B), with
+        ``info`` (B,) of :meth:`kkt_solve` and the ``delta`` (B,) used.  With W at
+        (x*, lam_g*) and the weights of :meth:`barrier_weights`,
+
+            M dx = -(d_p grad_w L) dp - J' Sigma_s (d_p g) dp,   dlam_g = Sigma_s (J dx + d_p g dp)
+
+        i.e. the interior-point linearisation of the optimality conditions at the returned
+        point: rows and bounds with a zero multiplier do not constrain the step, active ones
+        hold it with stiffness lam / slack.  M is taken at delta = 0 where it factorises with
+        the right inertia.  Where it does not -- M is singular whenever a variable has no
+        cost, row or active bound (this model's last heading-rate control moves only the final
+        heading, which nothing depends on), and a solution converged to 1e-8 can leave M
+        indefinite by as much -- the scenario is solved again as IPOPT's inertia correction
+        does: delta = first_hessian_perturbation, then times perturb_inc_fact_first, then
+        times perturb_inc_fact, up to max_hessian_perturbation (``info`` stays 1 beyond it).
+        A direction M does not determine comes out near 0.  The two parameter derivatives are central
+        differences of :meth:`evaluate`'s ``grad_l`` and ``g`` at p +- fd_step * dp_d, at fixed
+        (x, lam_g).  Their errors per unit dp: truncation fd_step^2 |d_p^3| / 6, and rounding
+        2.2e-16 |terms of grad_l| / fd_step.  At a solution the terms of grad_l cancel (grad f +
+        J' lam_g = -lam_x) by two to three orders, so keeping the rounding below 1e-10 of the
+        right-hand side needs fd_step >= 2e-4 ... 8e-4 (measured on race_track_2 solutions);
+        the default 1e-3 costs a truncation of 1.7e-7 |d_p^3|, at the level of what the
+        solve's own 1e-8 tolerance does to the result.  Scale dp so that fd_step * dp is a small move of p.  The exact parameter
+        tangent is not formed."""
+        d = np.asarray(dp, dtype=np.float64)
+        if d.ndim == 1:
+            d = d.reshape(-1, 1)
+        if d.ndim not in (2, 3) or d.shape[0] != self.np:
+            raise ValueError(f"dp: expected ({self.np},), ({self.np},nd) or ({self.np},nd,B), got shape {d.shape}")
+        x = np.asarray(sol["x"], dtype=np.float64).reshape(self.nw, -1)
+        lam = np.asarray(sol["lam_g"], dtype=np.float64).reshape(self.ng, -1)
+        B, nd = x.shape[1], d.shape[1]
+        P = np.asarray(p, dtype=np.float64).reshape(self.np, -1) * np.ones((1, B))
+        if d.ndim == 2:
+            d = np.repeat(d[:, :, None], B, axis=2)
+        sx, ss = self.barrier_weights(sol, lbx, ubx, lbg, ubg)
+        dgl, dg = np.empty((self.nw, nd, B)), np.empty((self.ng, nd, B))
+        for j in range(nd):
+            ep = self.evaluate(x, P + fd_step * d[:, j, :], lam_g=lam)
+            em = self.evaluate(x, P - fd_step * d[:, j, :], lam_g=lam)
+            dgl[:, j, :] = (ep["grad_l"] - em["grad_l"]) / (2 * fd_step)
+            dg[:, j, :] = (ep["g"] - em["g"]) / (2 * fd_step)
+        first, inc_first, inc, dmax = self._perturb
+        delta = np.zeros(B)
+        while True:
+            r = self.kkt_solve(x, P, r_w=-dgl, r_g=-(ss[:, None, :] * dg), lam_g=lam, sigma_x=sx, sigma_s=ss,
+                               delta=delta)
+            retry = r["info"] == 1
+            nxt = np.where(delta == 0.0, first, np.where(delta == first, inc_first * delta, inc * delta))
+            retry &= nxt <= dmax
+            if not np.any(retry):
+                break
+            delta = np.where(retry, nxt, delta)
+        return {"dx": r["dw"], "dlam_g": ss[:, None, :] * (r["jdw"] + dg), "info": r["info"], "delta": delta}
 
     def shift_device(self, p, u_sol, w_out, v_t, w_t, stream=None):
         """Closed-loop shift on device (Python/NMPC_TT.py:13-30), see nmpc_shift_dev."""
