@@ -328,6 +328,49 @@ int nmpc_kkt_solve_batch(nmpc_handle* h, int32_t B, int32_t nr,
                          const double* r_w, int64_t ld_r_w, const double* r_g, int64_t ld_r_g,
                          double* dw_out, double* dX_out, double* jdw_out, int32_t* info_out);
 
+/* Parameter-direction products at GIVEN points, for a whole batch: the parameter half of the
+ * function layer.  With L = obj_factor f + lam_g^T g (lam_g in CasADi's sign convention,
+ * NULL = zeros; obj_factor shared by the batch), for each of B scenarios and each of nd >= 0
+ * directions dp_d in parameter space (np long, the model's own layout [x0(nx); xt, yt, .; ...]):
+ *   jp_out  (ng nd x B)        = (dg/dp) dp_d; stage 0's rows are not zero here
+ *   hp_out  (nw nd x B)        = (d_p grad_w L) dp_d, the parameter tangent of nmpc_eval_batch's
+ *                                grad_l (lam_x absent) at fixed (x, lam_g)
+ *   dXp_out (nx(N+1) nd x B)   = (dX/dp) dp_d in X_out's layout; stage 0 is exactly dp_d[0:nx]
+ *   gp_out  (np x B)           = grad_p L, independent of the directions; with obj_factor = 1 at
+ *                                a solve's (x, lam_g) it is the negative of that solve's lam_p.
+ * The derivatives are exact (no difference step): the initial state through the tangent of the
+ * rollout and the Lagrangian adjoint, the target through the stage costs, an obstacle centre
+ * taken from p through that obstacle's rows, a cost weight taken from p through the cost term it
+ * scales.  An entry of p that nothing reads -- the target's third entry, a tail entry no
+ * obstacle or weight index names -- gives exactly 0 in gp_out, and its entry of dp is never
+ * read.
+ * Within a scenario direction d occupies [d n, (d+1) n) of each array.  dp is np nd per
+ * scenario; ld_dp = 0 shares one set of directions with every scenario (ld_dp = 0 and dp = I
+ * give the dense dg/dp and d_p grad_w L).  x, p and lam_g follow nmpc_products_batch_dev's
+ * leading-dimension rules.  Every output may be NULL, at least one must not be.  nd = 0 is
+ * allowed with gp_out alone: dp and the three directional outputs must then be NULL.
+ * Directions are independent of each other: a non-finite entry of dp gives non-finite output in
+ * its own direction only, and gp_out depends on no direction.  The no-gimbal model has nx = 5
+ * and nw = 3N.
+ * DEVICE pointers, enqueued on `stream`; never synchronises, and allocates nothing once the
+ * handle's workspace covers B (a solve's workspace does).
+ * A NULL handle, B <= 0, nd < 0, a NULL x or p, every output NULL, a directional output with
+ * nd = 0 or a NULL dp, a non-NULL dp with nd = 0, or a leading dimension that is neither 0 nor
+ * >= the vector length (np nd for dp) return NMPC_E_INVALID before any device call. */
+int nmpc_param_products_batch_dev(nmpc_handle* h, int32_t B, int32_t nd,
+                                  const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                                  const double* lam_g, int64_t ld_lam_g, double obj_factor,
+                                  const double* dp, int64_t ld_dp,
+                                  double* jp_out, double* hp_out, double* dXp_out, double* gp_out,
+                                  void* stream);
+
+/* Same with HOST pointers; synchronous (staged through the handle's device buffer). */
+int nmpc_param_products_batch(nmpc_handle* h, int32_t B, int32_t nd,
+                              const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                              const double* lam_g, int64_t ld_lam_g, double obj_factor,
+                              const double* dp, int64_t ld_dp,
+                              double* jp_out, double* hp_out, double* dXp_out, double* gp_out);
+
 /* Optional per-iteration trace (debugging / parity): when enabled, the next
  * solve records NMPC_TRACE_FIELDS doubles per iteration per scenario into a
  * device buffer readable with nmpc_read_trace (host pointer,

@@ -90,7 +90,33 @@ constexpr int kKktRv = kKktRd + 6 * kEvalStages;
 constexpr int kKktDu = kKktRv + 6 * kEvalStages;
 constexpr int kKktWs = kKktDu + 6 * kEvalStages;
 
+// DEVICE pointers, layouts and leading dimensions as nmpc_param_products_batch_dev
+// (include/nmpc_amd.h); x and p are required, dp with nd > 0, lam_g and every output may be null
+struct PprodIO {
+  const double *x, *p, *lam_g, *dp;
+  long long ld_x, ld_p, ld_lam_g, ld_dp;
+  double obj_factor;
+  int nd;
+  double *jp, *hp, *dXp, *gp;
+  double* ws;  // B x chunks x kPprodWs doubles of the handle's workspace
+};
+
+// Per-wavefront workspace of the parameter-products kernel (nmpc_pproducts.hip): the products
+// kernel's slices plus, per stage and obstacle, the three entries of lam_{k,o} grad^2 g_o (an
+// obstacle whose centre comes from p moves against the state, each by its own amount, so its
+// curvature cannot be summed into the stage's once for all directions).  Chunks as the
+// products kernel's; every solver class's workspace holds at least one slice (static_assert
+// in nmpc_pproducts.hip).
+constexpr int kPprodOc = kProdWs;
+constexpr int kPprodWs = kPprodOc + 3 * NMPC_MAX_OBS * kEvalStages;
+
 }  // namespace nmpc_impl
+
+// Enqueues the parameter-direction products of B scenarios on `stream`: B x chunks wavefronts,
+// wavefront (b, c) forming scenario b's directions c, c + chunks, ... and wavefront (b, 0) the
+// gradient grad_p L.  Same contract as nmpc_eval_launch.
+int nmpc_pproducts_launch(const nmpc_impl::Params* dprm, int B, int chunks, const nmpc_impl::PprodIO& io,
+                          void* stream);
 
 // Enqueues the KKT solves of B scenarios on `stream` (one wavefront per scenario, every
 // right-hand side on it: another wavefront would repeat the factorisation).  Same contract as

@@ -207,3 +207,6 @@ int nmpc_eval_launch(const Params* dprm, int B, const EvalIO& io, void* stream) 
 
 // the condensed KKT solves at given points: a third kernel of this unit
 #include "nmpc_kkt.hip"
+
+// the parameter-direction products at given points: a fourth kernel of this unit
+#include "nmpc_pproducts.hip"

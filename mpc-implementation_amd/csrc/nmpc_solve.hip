@@ -5763,13 +5763,10 @@ static int prod_check(const nmpc_handle* h, int32_t B, int32_t nv, const ProdArg
     return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
   return NMPC_OK;
 }
-// checked arguments, DEVICE pointers: workspace from the handle (sized like a solve's, grown
-// only when it does not cover B yet), then one launch.  A scenario's directions are dealt to
-// as many wavefronts as the class's per-scenario workspace holds slices for.
-static int prod_enqueue(nmpc_handle* h, int32_t B, int32_t nv, const ProdArgs& a, void* stream) {
-  const int per = h->ws_doubles > kProdWs ? h->ws_doubles : kProdWs;
-  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
-  int cap = per / kProdWs;
+// wavefronts per scenario of a products launch: `per` doubles of workspace per scenario hold
+// per / slice of them, nv directions occupy at most nv
+static int prod_chunks(int per, int slice, int32_t B, int32_t nv) {
+  int cap = per / slice;
   if (cap > kProdMaxChunks) cap = kProdMaxChunks;
   if (cap > nv) cap = nv;
   // every chunk repeats the scenario's set-up (rollout, derivatives, multipliers), so a batch
@@ -5779,6 +5776,15 @@ static int prod_enqueue(nmpc_handle* h, int32_t B, int32_t nv, const ProdArgs& a
   if (const char* e = std::getenv("NMPC_PRODUCTS_CHUNKS")) chunks = std::atoi(e);  // diagnostics
   if (chunks > cap) chunks = cap;
   if (chunks < 1) chunks = 1;
+  return chunks;
+}
+// checked arguments, DEVICE pointers: workspace from the handle (sized like a solve's, grown
+// only when it does not cover B yet), then one launch.  A scenario's directions are dealt to
+// as many wavefronts as the class's per-scenario workspace holds slices for.
+static int prod_enqueue(nmpc_handle* h, int32_t B, int32_t nv, const ProdArgs& a, void* stream) {
+  const int per = h->ws_doubles > kProdWs ? h->ws_doubles : kProdWs;
+  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
+  const int chunks = prod_chunks(per, kProdWs, B, nv);
   ProdIO io;
   io.x = a.x; io.p = a.p; io.lam_g = a.lam_g; io.v = a.v;
   io.ld_x = a.ld_x; io.ld_p = a.ld_p; io.ld_lam_g = a.ld_lam_g; io.ld_v = a.ld_v;
@@ -5946,6 +5952,102 @@ int nmpc_kkt_solve_batch(nmpc_handle* h, int32_t B, int32_t nr, const double* x,
     if (hout[i] && e == hipSuccess)
       e = hipMemcpy(hout[i], dout[i], (size_t)B * olen[i] * sizeof(double), hipMemcpyDeviceToHost);
   if (info_out && e == hipSuccess) e = hipMemcpy(info_out, dinfo, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
+// ---- parameter-direction products at given points (kernel: nmpc_pproducts.hip)
+struct PprodArgs {
+  const double *x, *p, *lam_g, *dp;
+  int64_t ld_x, ld_p, ld_lam_g, ld_dp;
+  double obj_factor;
+  double *jp, *hp, *dXp, *gp;
+};
+// the argument checks of both entry points: nothing here touches the device
+static int pprod_check(const nmpc_handle* h, int32_t B, int32_t nd, const PprodArgs& a) {
+  if (!h) return fail(NMPC_E_INVALID, "null handle");
+  if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
+  if (nd < 0) return fail(NMPC_E_INVALID, "nd < 0");
+  if (!a.x || !a.p) return fail(NMPC_E_INVALID, "required pointer is null (x, p)");
+  if (!a.jp && !a.hp && !a.dXp && !a.gp) return fail(NMPC_E_INVALID, "every output pointer is null");
+  if (nd == 0 && (a.dp || a.jp || a.hp || a.dXp))
+    return fail(NMPC_E_INVALID, "nd = 0 takes gp_out alone (dp and the directional outputs must be null)");
+  if (nd > 0 && !a.dp) return fail(NMPC_E_INVALID, "required pointer is null (dp with nd > 0)");
+  const Params& P = h->hp;
+  auto bad = [](const double* q, int64_t ld, int64_t n) { return q && ld != 0 && ld < n; };
+  if (bad(a.x, a.ld_x, P.nwE) || bad(a.p, a.ld_p, P.npE) || bad(a.lam_g, a.ld_lam_g, P.ng) ||
+      bad(a.dp, a.ld_dp, (int64_t)P.npE * nd))
+    return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
+  return NMPC_OK;
+}
+// checked arguments, DEVICE pointers: workspace and chunks as prod_enqueue, then one launch
+static int pprod_enqueue(nmpc_handle* h, int32_t B, int32_t nd, const PprodArgs& a, void* stream) {
+  const int per = h->ws_doubles > kPprodWs ? h->ws_doubles : kPprodWs;
+  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
+  const int chunks = prod_chunks(per, kPprodWs, B, nd);
+  PprodIO io;
+  io.x = a.x; io.p = a.p; io.lam_g = a.lam_g; io.dp = a.dp;
+  io.ld_x = a.ld_x; io.ld_p = a.ld_p; io.ld_lam_g = a.ld_lam_g; io.ld_dp = a.ld_dp;
+  io.obj_factor = a.obj_factor; io.nd = nd;
+  io.jp = a.jp; io.hp = a.hp; io.dXp = a.dXp; io.gp = a.gp;
+  io.ws = h->dws;
+  const hipError_t e = (hipError_t)nmpc_pproducts_launch(h->dprm, (int)B, chunks, io, stream);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("parameter products launch: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
+int nmpc_param_products_batch_dev(nmpc_handle* h, int32_t B, int32_t nd, const double* x, int64_t ld_x,
+                                  const double* p, int64_t ld_p, const double* lam_g, int64_t ld_lam_g,
+                                  double obj_factor, const double* dp, int64_t ld_dp, double* jp_out, double* hp_out,
+                                  double* dXp_out, double* gp_out, void* stream) {
+  const PprodArgs a{x, p, lam_g, dp, ld_x, ld_p, ld_lam_g, ld_dp, obj_factor, jp_out, hp_out, dXp_out, gp_out};
+  if (int rc = pprod_check(h, B, nd, a)) return rc;
+  return pprod_enqueue(h, B, nd, a, stream);
+}
+
+int nmpc_param_products_batch(nmpc_handle* h, int32_t B, int32_t nd, const double* x, int64_t ld_x, const double* p,
+                              int64_t ld_p, const double* lam_g, int64_t ld_lam_g, double obj_factor,
+                              const double* dp, int64_t ld_dp, double* jp_out, double* hp_out, double* dXp_out,
+                              double* gp_out) {
+  const PprodArgs a{x, p, lam_g, dp, ld_x, ld_p, ld_lam_g, ld_dp, obj_factor, jp_out, hp_out, dXp_out, gp_out};
+  if (int rc = pprod_check(h, B, nd, a)) return rc;
+  const Params& P = h->hp;
+  const size_t nw = P.nwE, ng = P.ng, np = P.npE, nX = (size_t)P.nxE * (P.N + 1);
+  // staging: the four inputs (absent ones take no room), then the four outputs
+  const double* src[4] = {x, p, lam_g, dp};
+  const int64_t ld[4] = {ld_x, ld_p, ld_lam_g, ld_dp};
+  const size_t vlen[4] = {nw, np, ng, np * (size_t)nd};
+  double* hout[4] = {jp_out, hp_out, dXp_out, gp_out};
+  const size_t olen[4] = {ng * (size_t)nd, nw * (size_t)nd, nX * (size_t)nd, np};
+  size_t n_in[4], total = 0;
+  for (int i = 0; i < 4; ++i) {
+    n_in[i] = !src[i] ? 0 : (ld[i] == 0 ? vlen[i] : (size_t)(B - 1) * (size_t)ld[i] + vlen[i]);
+    total += n_in[i];
+  }
+  for (int i = 0; i < 4; ++i) total += hout[i] ? (size_t)B * olen[i] : 0;
+  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
+  double* q = h->dbuf;
+  const double* din[4];
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 4; ++i) {
+    din[i] = src[i] ? q : nullptr;
+    if (src[i] && e == hipSuccess) e = hipMemcpy(q, src[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
+    q += n_in[i];
+  }
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
+  double* dout[4];
+  for (int i = 0; i < 4; ++i) {
+    dout[i] = hout[i] ? q : nullptr;
+    q += hout[i] ? (size_t)B * olen[i] : 0;
+  }
+  const PprodArgs d{din[0], din[1], din[2], din[3], ld_x, ld_p, ld_lam_g, ld_dp, obj_factor,
+                    dout[0], dout[1], dout[2], dout[3]};
+  if (int rc = pprod_enqueue(h, B, nd, d, nullptr)) return rc;
+  e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
+  for (int i = 0; i < 4; ++i)
+    if (hout[i] && e == hipSuccess)
+      e = hipMemcpy(hout[i], dout[i], (size_t)B * olen[i] * sizeof(double), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
   return NMPC_OK;
 }

@@ -439,6 +439,129 @@ class Solver:
         out = self._products(x, p, eye, 0, self.nw, lam_g, obj_factor, want=("hv",))
         return np.ascontiguousarray(out["hv"].transpose(2, 1, 0))
 
+    # ---- parameter-direction products at given points (nmpc_param_products_batch)
+    def _param_products(self, x, p, dp, ld_dp, nd, lam_g, obj_factor, want=("jp", "hp", "dXp", "gp")):
+        """dp: (1 or B, nd, np) C-contiguous, ld_dp 0 or np * nd (None with nd = 0).  Returns
+        (B, nd, n) arrays, and gp as (B, np)."""
+        args, B = [], 1
+        for name, a, n in (("x", x, self.nw), ("p", p, self.np), ("lam_g", lam_g, self.ng)):
+            if a is None:
+                if name != "lam_g":
+                    raise ValueError(f"{name} is required")
+                args.append((None, 0))
+                continue
+            a, ld = self._arg(a, n, 0.0, name)
+            if ld:
+                if B not in (1, a.shape[0]):
+                    raise ValueError(f"{name}: batch size {a.shape[0]} does not match {B}")
+                B = a.shape[0]
+            args.append((a, ld))
+        if ld_dp:
+            if B not in (1, dp.shape[0]):
+                raise ValueError(f"dp: batch size {dp.shape[0]} does not match {B}")
+            B = dp.shape[0]
+        sizes = {"jp": self.ng, "hp": self.nw, "dXp": self.nX}
+        out = {k: np.empty((B, nd, sizes[k])) for k in want if k != "gp"}
+        if "gp" in want:
+            out["gp"] = np.empty((B, self.np))
+        ins = []
+        for a, ld in args:
+            ins += [_dptr(a) if a is not None else None, ld]
+        _lib.check(_lib.lib().nmpc_param_products_batch(
+            self._h, B, nd, *ins, float(obj_factor), _dptr(dp) if dp is not None else None, ld_dp,
+            *[_dptr(out[k]) if k in out else None for k in ("jp", "hp", "dXp", "gp")]))
+        return out
+
+    def param_products(self, x, p, dp, lam_g=None, obj_factor=1.0):
+        """Exact products with the parameter derivatives at the given points, on the GPU, with
+        L = obj_factor f + lam_g' g: ``jp`` (ng,nd,B) = (dg/dp) dp, ``hp`` (nw,nd,B) =
+        (d_p grad_w L) dp (the change of :meth:`evaluate`'s ``grad_l`` with p at fixed x, lam_g),
+        ``dXp`` (nX,nd,B) = (dX/dp) dp, and ``gp`` (np,B) = grad_p L (the negative of a solve's
+        ``lam_p`` at its x, lam_g).  x, p, lam_g as :meth:`evaluate`'s; ``dp`` is one direction
+        (np,), directions (np,nd) shared by the batch, or (np,nd,B).  Entries of p that nothing
+        reads give exactly 0 in gp, and their entries of dp are never read.  ``dp=None`` asks
+        for ``gp`` alone (no directions)."""
+        if dp is None:
+            out = self._param_products(x, p, None, 0, 0, lam_g, obj_factor, want=("gp",))
+            return {"gp": np.ascontiguousarray(out["gp"].T)}
+        a = np.asarray(dp, dtype=np.float64)
+        if a.ndim == 1:
+            a = a.reshape(-1, 1)
+        if a.ndim not in (2, 3) or a.shape[0] != self.np or a.shape[1] < 1:
+            raise ValueError(f"dp: expected ({self.np},), ({self.np},nd) or ({self.np},nd,B), got shape {a.shape}")
+        nd = a.shape[1]
+        if a.ndim == 2:
+            dd, ld_dp = np.ascontiguousarray(a.T).reshape(1, nd, self.np), 0
+        else:
+            dd, ld_dp = np.ascontiguousarray(a.transpose(2, 1, 0)), self.np * nd
+        out = self._param_products(x, p, dd, ld_dp, nd, lam_g, obj_factor)
+        return {k: np.ascontiguousarray(t.transpose(2, 1, 0) if t.ndim == 3 else t.T) for k, t in out.items()}
+
+    def param_products_device(self, x, p, dp, out: dict, lam_g=None, obj_factor=1.0, stream=None):
+        """Device path of :meth:`param_products`: torch CUDA float64 tensors, x, p, lam_g
+        scenario-major (B, n) or shared (n,); ``dp`` is (B, nd, np) or shared (nd, np), or None
+        when only gp is asked for; ``out`` holds preallocated device tensors, any of jp (B,nd,ng),
+        hp (B,nd,nw), dXp (B,nd,nX), gp (B,np).  Enqueued on ``stream`` (default = current);
+        never synchronises the host."""
+        import torch  # plumbing only: device memory and streams
+
+        keys = ("jp", "hp", "dXp")
+        given = [out[k] for k in keys if out.get(k) is not None]
+        gp = out.get("gp")
+        if not given and gp is None:
+            raise ValueError("param_products_device: out holds none of " + ", ".join(keys + ("gp",)))
+        if given and dp is None:
+            raise ValueError("param_products_device: dp is required for a directional output")
+        B = given[0].shape[0] if given else gp.shape[0]
+        nd = 0 if dp is None else dp.shape[-2]
+
+        def dv(t, n):
+            if t is None:
+                return C.c_void_p(0), 0
+            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous()
+            if t.dim() == 1:
+                assert t.shape[0] == n
+                return C.c_void_p(t.data_ptr()), 0
+            assert t.shape == (B, n), (tuple(t.shape), (B, n))
+            return C.c_void_p(t.data_ptr()), n
+
+        ins = []
+        for t, n in ((x, self.nw), (p, self.np), (lam_g, self.ng)):
+            ins += list(dv(t, n))
+        if dp is None:
+            dpp, ld_dp = C.c_void_p(0), 0
+        else:
+            assert dp.dtype == torch.float64 and dp.is_cuda and dp.is_contiguous()
+            assert tuple(dp.shape) in ((nd, self.np), (B, nd, self.np)), tuple(dp.shape)
+            dpp, ld_dp = C.c_void_p(dp.data_ptr()), (0 if dp.dim() == 2 else nd * self.np)
+        outs = []
+        for k, n in zip(keys, (self.ng, self.nw, self.nX)):
+            t = out.get(k)
+            if t is not None:
+                assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B, nd, n), k
+            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
+        if gp is not None:
+            assert gp.dtype == torch.float64 and gp.is_cuda and gp.is_contiguous() and tuple(gp.shape) == (B, self.np)
+        outs.append(C.c_void_p(gp.data_ptr()) if gp is not None else C.c_void_p(0))
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        _lib.check(_lib.lib().nmpc_param_products_batch_dev(self._h, B, nd, *ins, float(obj_factor), dpp, ld_dp,
+                                                            *outs, C.c_void_p(stream.cuda_stream)))
+
+    def param_jacobian(self, x, p):
+        """Dense dg/dp (ng,np,B) at the given points: the identity directions, shared by the
+        batch, through :meth:`param_products`' kernel."""
+        eye = np.eye(self.np).reshape(1, self.np, self.np)
+        out = self._param_products(x, p, eye, 0, self.np, None, 1.0, want=("jp",))
+        return np.ascontiguousarray(out["jp"].transpose(2, 1, 0))
+
+    def param_cross(self, x, p, lam_g=None, obj_factor=1.0):
+        """Dense d_p grad_w L (nw,np,B), L = obj_factor f + lam_g' g, column d being the
+        derivative with respect to p_d (its transpose applied to y serves reverse mode)."""
+        eye = np.eye(self.np).reshape(1, self.np, self.np)
+        out = self._param_products(x, p, eye, 0, self.np, lam_g, obj_factor, want=("hp",))
+        return np.ascontiguousarray(out["hp"].transpose(2, 1, 0))
+
     # ---- condensed KKT solves at given points (nmpc_kkt_solve_batch: the Newton-step operator)
     def _rhs(self, r, n: int, name: str):
         """(n,), (n,nr) or (n,nr,B) -> ((1 or B, nr, n) C-contiguous, leading dimension, nr)."""
@@ -607,7 +730,7 @@ class Solver:
         sx[fx] = np.inf
         return sx, ss
 
-    def sensitivity(self, sol: dict, lbx, ubx, lbg, ubg, p, dp, fd_step: float = 1e-3):
+    def sensitivity(self, sol: dict, lbx, ubx, lbg, ubg, p, dp, fd_step: float = 1e-3, tangent: str = "fd"):
         """First-order change of a solution with the parameters: ``dx`` (nw,nd,B) = dx*/dp dp_d
         and ``dlam_g`` (ng,nd,B) for the directions ``dp`` (np,), (np,nd) or (np,nd,B), with
         ``info`` (B,) of :meth:`kkt_solve` and the ``delta`` (B,) used.  With W at
@@ -631,8 +754,12 @@ class Solver:
         J' lam_g = -lam_x) by two to three orders, so keeping the rounding below 1e-10 of the
         right-hand side needs fd_step >= 2e-4 ... 8e-4 (measured on race_track_2 solutions);
         the default 1e-3 costs a truncation of 1.7e-7 |d_p^3|, at the level of what the
-        solve's own 1e-8 tolerance does to the result.  Scale dp so that fd_step * dp is a small move of p.  The exact parameter
-        tangent is not formed."""
+        solve's own 1e-8 tolerance does to the result.  Scale dp so that fd_step * dp is a small move of p.  ``tangent="exact"``
+        takes both parameter derivatives from one :meth:`param_products` call instead (``hp`` and
+        ``jp`` alone, at (x*, lam_g*)): no difference step, ``fd_step`` is ignored, and the weights,
+        the delta ladder and the outputs are the same."""
+        if tangent not in ("fd", "exact"):
+            raise ValueError(f"tangent: expected 'fd' or 'exact', got {tangent!r}")
         d = np.asarray(dp, dtype=np.float64)
         if d.ndim == 1:
             d = d.reshape(-1, 1)
@@ -645,12 +772,17 @@ class Solver:
         if d.ndim == 2:
             d = np.repeat(d[:, :, None], B, axis=2)
         sx, ss = self.barrier_weights(sol, lbx, ubx, lbg, ubg)
-        dgl, dg = np.empty((self.nw, nd, B)), np.empty((self.ng, nd, B))
-        for j in range(nd):
-            ep = self.evaluate(x, P + fd_step * d[:, j, :], lam_g=lam)
-            em = self.evaluate(x, P - fd_step * d[:, j, :], lam_g=lam)
-            dgl[:, j, :] = (ep["grad_l"] - em["grad_l"]) / (2 * fd_step)
-            dg[:, j, :] = (ep["g"] - em["g"]) / (2 * fd_step)
+        if tangent == "exact":
+            dd = np.ascontiguousarray(d.transpose(2, 1, 0))  # (B, nd, np)
+            pp = self._param_products(x, P, dd, self.np * nd, nd, lam, 1.0, want=("jp", "hp"))
+            dgl, dg = (np.ascontiguousarray(pp[k].transpose(2, 1, 0)) for k in ("hp", "jp"))
+        else:
+            dgl, dg = np.empty((self.nw, nd, B)), np.empty((self.ng, nd, B))
+            for j in range(nd):
+                ep = self.evaluate(x, P + fd_step * d[:, j, :], lam_g=lam)
+                em = self.evaluate(x, P - fd_step * d[:, j, :], lam_g=lam)
+                dgl[:, j, :] = (ep["grad_l"] - em["grad_l"]) / (2 * fd_step)
+                dg[:, j, :] = (ep["g"] - em["g"]) / (2 * fd_step)
         first, inc_first, inc, dmax = self._perturb
         delta = np.zeros(B)
         while True:
