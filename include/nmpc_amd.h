@@ -371,6 +371,48 @@ int nmpc_param_products_batch(nmpc_handle* h, int32_t B, int32_t nd,
                               const double* dp, int64_t ld_dp,
                               double* jp_out, double* hp_out, double* dXp_out, double* gp_out);
 
+/* Adjoint (vector-Jacobian) products at GIVEN points, for a whole batch: the transposed half of
+ * the function layer, what reverse-mode differentiation of anything built on g, grad_w L or X
+ * needs (a loss on the applied control pulled back to cost weights from p -- the reference's
+ * replay over weight pairs at w1_pidx --, to obstacle centres, to the initial state).  With
+ * L = obj_factor f + lam_g^T g (lam_g in CasADi's sign convention, NULL = zeros; obj_factor
+ * shared by the batch) and W = obj_factor grad^2 f + sum_i lam_g_i grad^2 g_i, for each of B
+ * scenarios and each of na >= 1 seeds (y_d on g, z_d on grad_w L, Xb_d on X):
+ *   wbar_out (nw na x B) = J_g^T y_d + W z_d + (dX/dw)^T Xb_d
+ *   pbar_out (np na x B) = (dg/dp)^T y_d + (d_p grad_w L)^T z_d + (dX/dp)^T Xb_d
+ * the transposes of nmpc_products_batch_dev's and nmpc_param_products_batch_dev's maps, formed
+ * exactly by one forward tangent (z alone needs it) and one reverse sweep per seed, never as
+ * matrices.  y is ng na per scenario, z nw na, Xb nx(N+1) na in X_out's layout; each of the
+ * three may be NULL and then contributes nothing (its term is not formed), at least one must
+ * not be.  Stage 0's entries of y and Xb are read: (dg/dp) and (dX/dp) have stage-0 rows, and
+ * with Xb alone the x0 block of pbar receives Xb's stage 0 once.  An entry of p that nothing
+ * reads gives exactly 0 in pbar_out.  The gradients of f itself are nmpc_eval_batch's
+ * grad_f_out and nmpc_param_products_batch's gp_out and are not repeated here.
+ * Within a scenario seed d occupies [d n, (d+1) n) of each array; a leading dimension of 0
+ * shares one set of seeds with every scenario.  x, p and lam_g follow
+ * nmpc_products_batch_dev's leading-dimension rules.  Either output may be NULL, not both.
+ * Seeds are independent of each other: a non-finite entry of one seed gives non-finite output
+ * for that seed only.  The no-gimbal model has nx = 5 and nw = 3N.
+ * DEVICE pointers, enqueued on `stream`; never synchronises, and allocates nothing once the
+ * handle's workspace covers B (a solve's workspace does).
+ * A NULL handle, B <= 0, na <= 0, a NULL x or p, y, z and Xb all NULL, both outputs NULL, or a
+ * leading dimension that is neither 0 nor >= the vector length (ng na, nw na, nx(N+1) na for
+ * the seeds) return NMPC_E_INVALID before any device call. */
+int nmpc_adjoint_products_batch_dev(nmpc_handle* h, int32_t B, int32_t na,
+                                    const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                                    const double* lam_g, int64_t ld_lam_g, double obj_factor,
+                                    const double* y, int64_t ld_y, const double* z, int64_t ld_z,
+                                    const double* Xb, int64_t ld_Xb,
+                                    double* wbar_out, double* pbar_out, void* stream);
+
+/* Same with HOST pointers; synchronous (staged through the handle's device buffer). */
+int nmpc_adjoint_products_batch(nmpc_handle* h, int32_t B, int32_t na,
+                                const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                                const double* lam_g, int64_t ld_lam_g, double obj_factor,
+                                const double* y, int64_t ld_y, const double* z, int64_t ld_z,
+                                const double* Xb, int64_t ld_Xb,
+                                double* wbar_out, double* pbar_out);
+
 /* Optional per-iteration trace (debugging / parity): when enabled, the next
  * solve records NMPC_TRACE_FIELDS doubles per iteration per scenario into a
  * device buffer readable with nmpc_read_trace (host pointer,

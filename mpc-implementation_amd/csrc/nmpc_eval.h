@@ -110,7 +110,30 @@ struct PprodIO {
 constexpr int kPprodOc = kProdWs;
 constexpr int kPprodWs = kPprodOc + 3 * NMPC_MAX_OBS * kEvalStages;
 
+// DEVICE pointers, layouts and leading dimensions as nmpc_adjoint_products_batch_dev
+// (include/nmpc_amd.h); x and p are required, one of the seeds y / z / Xb and one of wbar / pbar
+struct AdjIO {
+  const double *x, *p, *lam_g, *y, *z, *Xb;
+  long long ld_x, ld_p, ld_lam_g, ld_y, ld_z, ld_Xb;
+  double obj_factor;
+  int na;
+  double *wbar, *pbar;
+  double* ws;  // B x chunks x kAdjWs doubles of the handle's workspace
+};
+
+// Per-wavefront workspace of the adjoint-products kernel (nmpc_adjoint.hip): the
+// parameter-products kernel's slices, used the same way (the gradient slice holds each seed's
+// stage sources, the per-obstacle curvature serves the obstacle centres' entries of pbar).
+// Chunks as the products kernel's; every solver class's workspace holds at least one slice
+// (static_assert in nmpc_adjoint.hip).
+constexpr int kAdjWs = kPprodWs;
+
 }  // namespace nmpc_impl
+
+// Enqueues the adjoint products of B scenarios on `stream`: B x chunks wavefronts, wavefront
+// (b, c) forming scenario b's seeds c, c + chunks, ...  Same contract as nmpc_eval_launch.
+int nmpc_adjoint_launch(const nmpc_impl::Params* dprm, int B, int chunks, const nmpc_impl::AdjIO& io,
+                        void* stream);
 
 // Enqueues the parameter-direction products of B scenarios on `stream`: B x chunks wavefronts,
 // wavefront (b, c) forming scenario b's directions c, c + chunks, ... and wavefront (b, 0) the

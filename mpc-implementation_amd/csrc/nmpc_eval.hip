@@ -210,3 +210,6 @@ int nmpc_eval_launch(const Params* dprm, int B, const EvalIO& io, void* stream) 
 
 // the parameter-direction products at given points: a fourth kernel of this unit
 #include "nmpc_pproducts.hip"
+
+// the adjoint (transposed) products at given points: a fifth kernel of this unit
+#include "nmpc_adjoint.hip"

@@ -7,7 +7,7 @@
 // cost weights taken from p -- differentiated exactly, at any point.
 //
 // Part of the evaluation kernel's translation unit like nmpc_products.hip (nmpc_eval.hip
-// includes this file last), so the derivatives are the text the solver compiles:
+// includes this file after nmpc_kkt.hip), so the derivatives are the text the solver compiles:
 // Solver::rollout, stage_cost, derivs<true, true>, adjoint, stage_AB, row_jd, grad_u.
 //
 // Execution model: the products kernel's.  One wavefront per (scenario, direction chunk),

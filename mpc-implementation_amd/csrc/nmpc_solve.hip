@@ -6052,6 +6052,103 @@ int nmpc_param_products_batch(nmpc_handle* h, int32_t B, int32_t nd, const doubl
   return NMPC_OK;
 }
 
+// ---- adjoint (transposed) products at given points (kernel: nmpc_adjoint.hip)
+struct AdjArgs {
+  const double *x, *p, *lam_g, *y, *z, *Xb;
+  int64_t ld_x, ld_p, ld_lam_g, ld_y, ld_z, ld_Xb;
+  double obj_factor;
+  double *wbar, *pbar;
+};
+// the argument checks of both entry points: nothing here touches the device
+static int adj_check(const nmpc_handle* h, int32_t B, int32_t na, const AdjArgs& a) {
+  if (!h) return fail(NMPC_E_INVALID, "null handle");
+  if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
+  if (na <= 0) return fail(NMPC_E_INVALID, "na <= 0");
+  if (!a.x || !a.p) return fail(NMPC_E_INVALID, "required pointer is null (x, p)");
+  if (!a.y && !a.z && !a.Xb) return fail(NMPC_E_INVALID, "every seed pointer is null (y, z, Xb)");
+  if (!a.wbar && !a.pbar) return fail(NMPC_E_INVALID, "every output pointer is null (wbar, pbar)");
+  const Params& P = h->hp;
+  auto bad = [](const double* q, int64_t ld, int64_t n) { return q && ld != 0 && ld < n; };
+  if (bad(a.x, a.ld_x, P.nwE) || bad(a.p, a.ld_p, P.npE) || bad(a.lam_g, a.ld_lam_g, P.ng) ||
+      bad(a.y, a.ld_y, (int64_t)P.ng * na) || bad(a.z, a.ld_z, (int64_t)P.nwE * na) ||
+      bad(a.Xb, a.ld_Xb, (int64_t)P.nxE * (P.N + 1) * na))
+    return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
+  return NMPC_OK;
+}
+// checked arguments, DEVICE pointers: workspace and chunks as prod_enqueue, then one launch
+static int adj_enqueue(nmpc_handle* h, int32_t B, int32_t na, const AdjArgs& a, void* stream) {
+  const int per = h->ws_doubles > kAdjWs ? h->ws_doubles : kAdjWs;
+  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
+  const int chunks = prod_chunks(per, kAdjWs, B, na);
+  AdjIO io;
+  io.x = a.x; io.p = a.p; io.lam_g = a.lam_g; io.y = a.y; io.z = a.z; io.Xb = a.Xb;
+  io.ld_x = a.ld_x; io.ld_p = a.ld_p; io.ld_lam_g = a.ld_lam_g; io.ld_y = a.ld_y; io.ld_z = a.ld_z;
+  io.ld_Xb = a.ld_Xb;
+  io.obj_factor = a.obj_factor; io.na = na;
+  io.wbar = a.wbar; io.pbar = a.pbar;
+  io.ws = h->dws;
+  const hipError_t e = (hipError_t)nmpc_adjoint_launch(h->dprm, (int)B, chunks, io, stream);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("adjoint products launch: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
+int nmpc_adjoint_products_batch_dev(nmpc_handle* h, int32_t B, int32_t na, const double* x, int64_t ld_x,
+                                    const double* p, int64_t ld_p, const double* lam_g, int64_t ld_lam_g,
+                                    double obj_factor, const double* y, int64_t ld_y, const double* z, int64_t ld_z,
+                                    const double* Xb, int64_t ld_Xb, double* wbar_out, double* pbar_out,
+                                    void* stream) {
+  const AdjArgs a{x, p, lam_g, y, z, Xb, ld_x, ld_p, ld_lam_g, ld_y, ld_z, ld_Xb, obj_factor, wbar_out, pbar_out};
+  if (int rc = adj_check(h, B, na, a)) return rc;
+  return adj_enqueue(h, B, na, a, stream);
+}
+
+int nmpc_adjoint_products_batch(nmpc_handle* h, int32_t B, int32_t na, const double* x, int64_t ld_x,
+                                const double* p, int64_t ld_p, const double* lam_g, int64_t ld_lam_g,
+                                double obj_factor, const double* y, int64_t ld_y, const double* z, int64_t ld_z,
+                                const double* Xb, int64_t ld_Xb, double* wbar_out, double* pbar_out) {
+  const AdjArgs a{x, p, lam_g, y, z, Xb, ld_x, ld_p, ld_lam_g, ld_y, ld_z, ld_Xb, obj_factor, wbar_out, pbar_out};
+  if (int rc = adj_check(h, B, na, a)) return rc;
+  const Params& P = h->hp;
+  const size_t nw = P.nwE, ng = P.ng, np = P.npE, nX = (size_t)P.nxE * (P.N + 1);
+  // staging: the six inputs (absent ones take no room), then the two outputs
+  const double* src[6] = {x, p, lam_g, y, z, Xb};
+  const int64_t ld[6] = {ld_x, ld_p, ld_lam_g, ld_y, ld_z, ld_Xb};
+  const size_t vlen[6] = {nw, np, ng, ng * (size_t)na, nw * (size_t)na, nX * (size_t)na};
+  double* hout[2] = {wbar_out, pbar_out};
+  const size_t olen[2] = {nw * (size_t)na, np * (size_t)na};
+  size_t n_in[6], total = 0;
+  for (int i = 0; i < 6; ++i) {
+    n_in[i] = !src[i] ? 0 : (ld[i] == 0 ? vlen[i] : (size_t)(B - 1) * (size_t)ld[i] + vlen[i]);
+    total += n_in[i];
+  }
+  for (int i = 0; i < 2; ++i) total += hout[i] ? (size_t)B * olen[i] : 0;
+  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
+  double* q = h->dbuf;
+  const double* din[6];
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 6; ++i) {
+    din[i] = src[i] ? q : nullptr;
+    if (src[i] && e == hipSuccess) e = hipMemcpy(q, src[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
+    q += n_in[i];
+  }
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
+  double* dout[2];
+  for (int i = 0; i < 2; ++i) {
+    dout[i] = hout[i] ? q : nullptr;
+    q += hout[i] ? (size_t)B * olen[i] : 0;
+  }
+  const AdjArgs d{din[0], din[1], din[2], din[3], din[4], din[5], ld_x, ld_p, ld_lam_g, ld_y, ld_z, ld_Xb,
+                  obj_factor, dout[0], dout[1]};
+  if (int rc = adj_enqueue(h, B, na, d, nullptr)) return rc;
+  e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
+  for (int i = 0; i < 2; ++i)
+    if (hout[i] && e == hipSuccess)
+      e = hipMemcpy(hout[i], dout[i], (size_t)B * olen[i] * sizeof(double), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
 int nmpc_shift_dev(nmpc_handle* h, int32_t B, double* p, int64_t ld_p, const double* u_sol, double* w_out,
                    const double* v_t, const double* w_t, void* stream) {
   if (!h) return fail(NMPC_E_INVALID, "null handle");

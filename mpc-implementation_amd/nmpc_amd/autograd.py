@@ -1,0 +1,68 @@
+"""``torch.autograd`` over the batched solve: the NMPC law as a differentiable layer.
+
+    x, X = nmpc_amd.autograd.solve(solver, p, lbx, ubx, lbg, ubg)
+    loss(x, X).backward()          # p.grad: d loss / d p, every entry of p at once
+
+Forward is :meth:`Solver.solve_device`; backward is :meth:`Solver.sensitivity_adjoint` (one KKT
+solve with one right-hand side and one transposed product per scenario, whatever np is).  This
+module holds no mathematics of its own.  torch is imported lazily, as the device methods do.
+"""
+from __future__ import annotations
+
+import functools
+
+import numpy as np
+
+_SUCCESS = (0, 1)
+
+
+@functools.lru_cache(maxsize=None)
+def _function():
+    import torch
+
+    class _Solve(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, p, solver, lbx, ubx, lbg, ubg, x0):
+            assert p.dtype == torch.float64 and p.is_cuda and p.dim() == 2 and p.shape[1] == solver.np, tuple(p.shape)
+            B = p.shape[0]
+            f64 = dict(dtype=torch.float64, device=p.device)
+            pd = p.detach().contiguous()
+            bounds = [np.asarray(v, dtype=np.float64) for v in (lbx, ubx, lbg, ubg)]
+            dev = [torch.tensor(np.ascontiguousarray(v.T if v.ndim == 2 else v), **f64) for v in bounds]
+            w0 = torch.zeros(B, solver.nw, **f64) if x0 is None else x0.detach().contiguous()
+            out = {"x": torch.empty(B, solver.nw, **f64), "g": torch.empty(B, solver.ng, **f64),
+                   "lam_x": torch.empty(B, solver.nw, **f64), "lam_g": torch.empty(B, solver.ng, **f64),
+                   "X": torch.empty(B, solver.nX, **f64),
+                   "status": torch.empty(B, dtype=torch.int32, device=p.device)}
+            solver.solve_device(w0, *dev, pd, out)
+            ctx.set_materialize_grads(False)  # an output the loss does not read seeds nothing
+            ctx.solver, ctx.bounds = solver, bounds
+            # the solution as sensitivity_adjoint takes it: columns per scenario, on the host
+            ctx.sol = {k: out[k].cpu().numpy().T for k in ("x", "g", "lam_x", "lam_g")}
+            ctx.p = pd.cpu().numpy().T
+            ctx.status = out["status"].cpu().numpy()
+            return out["x"], out["X"]
+
+        @staticmethod
+        def backward(ctx, x_bar, X_bar):
+            def seed(t):  # (B, n) -> (n, 1, B)
+                return None if t is None else np.ascontiguousarray(t.detach().cpu().numpy().T[:, None, :])
+
+            r = ctx.solver.sensitivity_adjoint(ctx.sol, *ctx.bounds, ctx.p, x_bar=seed(x_bar), X_bar=seed(X_bar))
+            g = np.ascontiguousarray(r["pbar"][:, 0, :].T)  # (B, np); NaN rows where info != 0
+            g[~np.isin(ctx.status, _SUCCESS)] = np.nan
+            ref = x_bar if x_bar is not None else X_bar
+            return (torch.tensor(g, dtype=torch.float64, device=ref.device),) + (None,) * 6
+
+    return _Solve
+
+
+def solve(solver, p, lbx, ubx, lbg, ubg, x0=None):
+    """Solves the batch at the parameters ``p`` -- a (B, np) float64 CUDA tensor that may require
+    grad -- and returns the solution ``x`` (B, nw) and its state trajectory ``X`` (B, nx(N+1)) as
+    CUDA tensors through which ``backward`` reaches p.  ``lbx``, ``ubx``, ``lbg``, ``ubg`` are
+    host arrays as :meth:`Solver.__call__` takes them ((n,) or (n,B)); ``x0`` is a (B, nw) CUDA
+    tensor, absent = zeros.  A scenario that did not converge (status not 0 or 1), or whose KKT
+    matrix does not factorise along the delta ladder (``info`` 1), gets a NaN row in p's gradient.
+    Equality rows raise in backward, as :meth:`Solver.barrier_weights` does."""
+    return _function().apply(p, solver, lbx, ubx, lbg, ubg, x0)

@@ -562,6 +562,114 @@ class Solver:
         out = self._param_products(x, p, eye, 0, self.np, lam_g, obj_factor, want=("hp",))
         return np.ascontiguousarray(out["hp"].transpose(2, 1, 0))
 
+    # ---- adjoint (transposed) products at given points (nmpc_adjoint_products_batch)
+    def adjoint_products(self, x, p, y=None, z=None, Xbar=None, lam_g=None, obj_factor=1.0,
+                         want=("wbar", "pbar")):
+        """Exact vector-Jacobian products of the map (w, p) -> (g, grad_w L, X) at the given
+        points, on the GPU, with L = obj_factor f + lam_g' g and W its Hessian in w:
+        ``wbar`` (nw,na,B) = J' y + W z + (dX/dw)' Xbar and ``pbar`` (np,na,B) = (dg/dp)' y +
+        (d_p grad_w L)' z + (dX/dp)' Xbar -- the transposes of :meth:`products` and
+        :meth:`param_products`, what reverse mode needs, without forming a matrix.  x, p, lam_g
+        as :meth:`evaluate`'s; each seed ``y`` (ng rows), ``z`` (nw), ``Xbar`` (nX) is one seed
+        (n,), seeds (n,na) shared by the batch, or (n,na,B); an absent seed contributes nothing,
+        at least one is required and all given ones carry the same na.  Entries of p that
+        nothing reads give exactly 0 in pbar.  ``want`` names the outputs to form."""
+        args, B = [], 1
+
+        def batch(name, rows):
+            nonlocal B
+            if B not in (1, rows):
+                raise ValueError(f"{name}: batch size {rows} does not match {B}")
+            B = rows
+
+        for name, a, n in (("x", x, self.nw), ("p", p, self.np), ("lam_g", lam_g, self.ng)):
+            if a is None:
+                if name != "lam_g":
+                    raise ValueError(f"{name} is required")
+                args.append((None, 0))
+                continue
+            a, ld = self._arg(a, n, 0.0, name)
+            if ld:
+                batch(name, a.shape[0])
+            args.append((a, ld))
+        na, seeds = None, []
+        for name, r, n in (("y", y, self.ng), ("z", z, self.nw), ("Xbar", Xbar, self.nX)):
+            if r is None:
+                seeds.append((None, 0))
+                continue
+            a, ld, k = self._rhs(r, n, name)
+            if na not in (None, k):
+                raise ValueError(f"{name}: {k} seeds do not match {na}")
+            na = k
+            if ld:
+                batch(name, a.shape[0])
+            seeds.append((a, ld))
+        if na is None:
+            raise ValueError("y, z or Xbar is required")
+        want = tuple(want)
+        if not want or any(k not in ("wbar", "pbar") for k in want):
+            raise ValueError(f"want: expected 'wbar' and / or 'pbar', got {want!r}")
+        sizes = {"wbar": self.nw, "pbar": self.np}
+        out = {k: np.empty((B, na, sizes[k])) for k in ("wbar", "pbar") if k in want}
+        ins = []
+        for a, ld in args:
+            ins += [_dptr(a) if a is not None else None, ld]
+        ins.append(float(obj_factor))
+        for a, ld in seeds:
+            ins += [_dptr(a) if a is not None else None, ld]
+        _lib.check(_lib.lib().nmpc_adjoint_products_batch(
+            self._h, B, na, *ins, *[_dptr(out[k]) if k in out else None for k in ("wbar", "pbar")]))
+        return {k: np.ascontiguousarray(t.transpose(2, 1, 0)) for k, t in out.items()}
+
+    def adjoint_products_device(self, x, p, out: dict, y=None, z=None, Xbar=None, lam_g=None, obj_factor=1.0,
+                                stream=None):
+        """Device path of :meth:`adjoint_products`: torch CUDA float64 tensors, x, p, lam_g
+        scenario-major (B, n) or shared (n,); each seed is (B, na, n) or shared (na, n), or None;
+        ``out`` holds preallocated device tensors, wbar (B,na,nw) and / or pbar (B,na,np).
+        Enqueued on ``stream`` (default = current); never synchronises the host."""
+        import torch  # plumbing only: device memory and streams
+
+        keys = ("wbar", "pbar")
+        given = [out[k] for k in keys if out.get(k) is not None]
+        if not given:
+            raise ValueError("adjoint_products_device: out holds none of " + ", ".join(keys))
+        if y is None and z is None and Xbar is None:
+            raise ValueError("y, z or Xbar is required")
+        B, na = given[0].shape[0], given[0].shape[1]
+
+        def dv(t, n):
+            if t is None:
+                return C.c_void_p(0), 0
+            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous()
+            if t.dim() == 1:
+                assert t.shape[0] == n
+                return C.c_void_p(t.data_ptr()), 0
+            assert t.shape == (B, n), (tuple(t.shape), (B, n))
+            return C.c_void_p(t.data_ptr()), n
+
+        def sv(t, n, name):
+            if t is None:
+                return C.c_void_p(0), 0
+            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), name
+            assert tuple(t.shape) in ((na, n), (B, na, n)), (name, tuple(t.shape))
+            return C.c_void_p(t.data_ptr()), (0 if t.dim() == 2 else na * n)
+
+        ins = []
+        for t, n in ((x, self.nw), (p, self.np), (lam_g, self.ng)):
+            ins += list(dv(t, n))
+        ins.append(float(obj_factor))
+        ins += list(sv(y, self.ng, "y")) + list(sv(z, self.nw, "z")) + list(sv(Xbar, self.nX, "Xbar"))
+        outs = []
+        for k, n in zip(keys, (self.nw, self.np)):
+            t = out.get(k)
+            if t is not None:
+                assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B, na, n), k
+            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        _lib.check(_lib.lib().nmpc_adjoint_products_batch_dev(self._h, B, na, *ins, *outs,
+                                                              C.c_void_p(stream.cuda_stream)))
+
     # ---- condensed KKT solves at given points (nmpc_kkt_solve_batch: the Newton-step operator)
     def _rhs(self, r, n: int, name: str):
         """(n,), (n,nr) or (n,nr,B) -> ((1 or B, nr, n) C-contiguous, leading dimension, nr)."""
@@ -783,18 +891,71 @@ class Solver:
                 em = self.evaluate(x, P - fd_step * d[:, j, :], lam_g=lam)
                 dgl[:, j, :] = (ep["grad_l"] - em["grad_l"]) / (2 * fd_step)
                 dg[:, j, :] = (ep["g"] - em["g"]) / (2 * fd_step)
+        r, delta = self._kkt_ladder(x, P, -dgl, -(ss[:, None, :] * dg), lam, sx, ss)
+        return {"dx": r["dw"], "dlam_g": ss[:, None, :] * (r["jdw"] + dg), "info": r["info"], "delta": delta}
+
+    def _kkt_ladder(self, x, P, r_w, r_g, lam, sx, ss):
+        """:meth:`kkt_solve` at delta = 0, and again for the scenarios whose M does not factorise
+        with the right inertia along IPOPT's inertia-correction ladder (see :meth:`sensitivity`).
+        Returns the last solve's result and the delta (B,) used."""
         first, inc_first, inc, dmax = self._perturb
-        delta = np.zeros(B)
+        delta = np.zeros(x.shape[1])
         while True:
-            r = self.kkt_solve(x, P, r_w=-dgl, r_g=-(ss[:, None, :] * dg), lam_g=lam, sigma_x=sx, sigma_s=ss,
-                               delta=delta)
+            r = self.kkt_solve(x, P, r_w=r_w, r_g=r_g, lam_g=lam, sigma_x=sx, sigma_s=ss, delta=delta)
             retry = r["info"] == 1
             nxt = np.where(delta == 0.0, first, np.where(delta == first, inc_first * delta, inc * delta))
             retry &= nxt <= dmax
             if not np.any(retry):
                 break
             delta = np.where(retry, nxt, delta)
-        return {"dx": r["dw"], "dlam_g": ss[:, None, :] * (r["jdw"] + dg), "info": r["info"], "delta": delta}
+        return r, delta
+
+    def sensitivity_adjoint(self, sol: dict, lbx, ubx, lbg, ubg, p, x_bar=None, lam_g_bar=None, X_bar=None):
+        """Reverse mode of :meth:`sensitivity` with ``tangent="exact"``: for seeds ``x_bar`` on
+        x*, ``lam_g_bar`` on lam_g* and ``X_bar`` on X* -- each (n,), (n,na) or (n,na,B), absent
+        = zeros, at least one given -- ``pbar`` (np,na,B) with <pbar, dp> = <x_bar, dx> +
+        <lam_g_bar, dlam_g> + <X_bar, dX*> for every dp, at the cost of one right-hand side per
+        seed whatever np is.  The same barrier weights and delta ladder as :meth:`sensitivity`
+        (``info`` (B,), ``delta`` (B,)); M is symmetric, so with q = M^-1 (x_bar + (dX/dw)' X_bar
+        + J' Sigma_s lam_g_bar)
+
+            pbar = -(d_p grad_w L)' q + (dg/dp)' Sigma_s (lam_g_bar - J q) + (dX/dp)' X_bar
+
+        by :meth:`adjoint_products` at (x*, lam_g*); ``q`` (nw,na,B) and ``jq`` (ng,na,B) = J q
+        are returned beside it.  A fixed variable (lbx == ubx) ignores its
+        x_bar; a scenario whose ``info`` stays 1 gets NaN; equality rows raise, as
+        :meth:`barrier_weights` does."""
+        x = np.asarray(sol["x"], dtype=np.float64).reshape(self.nw, -1)
+        lam = np.asarray(sol["lam_g"], dtype=np.float64).reshape(self.ng, -1)
+        B = x.shape[1]
+        P = np.asarray(p, dtype=np.float64).reshape(self.np, -1) * np.ones((1, B))
+        seeds, na = {}, None
+        for name, v, n in (("x_bar", x_bar, self.nw), ("lam_g_bar", lam_g_bar, self.ng), ("X_bar", X_bar, self.nX)):
+            if v is None:
+                continue
+            a = np.asarray(v, dtype=np.float64)
+            if a.ndim == 1:
+                a = a.reshape(-1, 1)
+            if a.ndim not in (2, 3) or a.shape[0] != n or a.shape[1] < 1 or (a.ndim == 3 and a.shape[2] != B):
+                raise ValueError(f"{name}: expected ({n},), ({n},na) or ({n},na,{B}), got shape {a.shape}")
+            if na not in (None, a.shape[1]):
+                raise ValueError(f"{name}: {a.shape[1]} seeds do not match {na}")
+            na = a.shape[1]
+            seeds[name] = a if a.ndim == 3 else np.repeat(a[:, :, None], B, axis=2)
+        if not seeds:
+            raise ValueError("x_bar, lam_g_bar or X_bar is required")
+        sx, ss = self.barrier_weights(sol, lbx, ubx, lbg, ubg)
+        xb, lb, Xb = seeds.get("x_bar"), seeds.get("lam_g_bar"), seeds.get("X_bar")
+        r_w = xb
+        if Xb is not None:
+            zx = self.adjoint_products(x, P, Xbar=Xb, lam_g=lam, want=("wbar",))["wbar"]
+            r_w = zx if xb is None else xb + zx
+        sl = None if lb is None else ss[:, None, :] * lb
+        r, delta = self._kkt_ladder(x, P, r_w, sl, lam, sx, ss)
+        y = -(ss[:, None, :] * r["jdw"]) if sl is None else sl - ss[:, None, :] * r["jdw"]
+        pbar = self.adjoint_products(x, P, y=y, z=-r["dw"], Xbar=Xb, lam_g=lam, want=("pbar",))["pbar"]
+        pbar[:, :, r["info"] != 0] = np.nan
+        return {"pbar": pbar, "info": r["info"], "delta": delta, "q": r["dw"], "jq": r["jdw"]}
 
     def shift_device(self, p, u_sol, w_out, v_t, w_t, stream=None):
         """Closed-loop shift on device (Python/NMPC_TT.py:13-30), see nmpc_shift_dev."""
