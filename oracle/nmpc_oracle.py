@@ -571,24 +571,55 @@ class _Chol:
     plain factorisation (the committed fixtures); variant v > 0 factors P M P^T for a fixed
     symmetric permutation P of the variables (IpoptDense.la_variant): 1 reverses the
     order, 2 takes the even then the odd positions, 3 rotates by a third.  Each is the
-    same Newton step in exact arithmetic and differs from variant 0 by rounding alone."""
+    same Newton step in exact arithmetic and differs from variant 0 by rounding alone.
+
+    Variants 4..7 are the float32 leg (the kernel's linear_solver_fp32): the factor of
+    variant v - 4's P M P^T computed and applied in float32, followed by ONE step of iterative
+    refinement with the residual in fp64, x += solve32(b - M x).  Variant 8 is the float32
+    factor under the identity with NO refinement: the deliberately wrong reference of the
+    fp32 trace tests.  Variants 0..3 run exactly the code they always ran."""
+
+    PERMS = 4
+    UNREFINED32 = 8
 
     def __init__(self, M, variant=0):
         n = M.shape[0]
         self.perm = None
-        if variant == 1:
+        self.single = variant >= self.PERMS
+        self.refine = self.PERMS <= variant < 2 * self.PERMS
+        if variant > self.UNREFINED32 or variant < 0:
+            raise ValueError(f"la_variant {variant}")
+        pv = variant % self.PERMS
+        if pv == 1:
             self.perm = np.arange(n)[::-1]
-        elif variant == 2:
+        elif pv == 2:
             self.perm = np.concatenate([np.arange(0, n, 2), np.arange(1, n, 2)])
-        elif variant == 3:
+        elif pv == 3:
             self.perm = np.roll(np.arange(n), n // 3)
-        self.L = np.linalg.cholesky(M if self.perm is None else M[np.ix_(self.perm, self.perm)])
+        Mp = M if self.perm is None else M[np.ix_(self.perm, self.perm)]
+        if self.single:
+            self.M = Mp
+            M32 = Mp.astype(np.float32)
+            if not np.all(np.isfinite(M32)):
+                raise np.linalg.LinAlgError("float32 overflow")
+            self.L = np.linalg.cholesky(M32)
+        else:
+            self.L = np.linalg.cholesky(Mp)
+
+    def _solve32(self, b):
+        t = np.linalg.solve(self.L, b.astype(np.float32))
+        return np.linalg.solve(self.L.T, t).astype(np.float64)
 
     def solve(self, b):
         if self.perm is not None:
             b = b[self.perm]
-        t = np.linalg.solve(self.L, b)
-        x = np.linalg.solve(self.L.T, t)
+        if self.single:
+            x = self._solve32(b)
+            if self.refine:
+                x = x + self._solve32(b - self.M @ x)
+        else:
+            t = np.linalg.solve(self.L, b)
+            x = np.linalg.solve(self.L.T, t)
         if self.perm is None:
             return x
         out = np.empty_like(x)
@@ -605,7 +636,8 @@ class IpoptDense:
         (P M P^T, _Chol) -- mathematically the identical Newton step, different by
         rounding alone.  Running a step under both measures how far that
         step's result moves under rounding-level changes of the linear algebra
-        (tests/golden/gen_rounding_spread.py)."""
+        (tests/golden/gen_rounding_spread.py).  4..7 = the float32 factor of 0..3 with one fp64
+        refinement step, 8 = the float32 factor alone (_Chol; tests/trace_cases.py)."""
         self.prob = prob
         self.la_variant = int(la_variant)
         o = dict(IPOPT_DEFAULTS)

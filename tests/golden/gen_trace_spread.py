@@ -23,8 +23,14 @@ to fixed relative figures, trace_cases.FIXED_REL);
 tests/test_oracle.py checks that a 1e-7 error in the oracle's gradient, one obstacle row or
 Newton step fails that comparison by 10 x and more.
 
-    python tests/golden/gen_trace_spread.py [--check] [--jobs 8]
-        (--check: regenerate and compare with the committed file instead of writing it)
+A second fixture, tests/golden/trace_spread_fp32.npz, holds the same layout's lead, dev_abs and
+dev_rel for the fp32 leg on trace_cases.GATED: the deviation of the refined float32 variants
+(trace_cases.FP32_VARIANTS: a float32 Cholesky factor with one fp64 refinement step under the
+identity and the three permutations, also with the literal objective) from the plain fp64
+oracle, and the leading iterations on which all of them take its iteration and trial counts.
+
+    python tests/golden/gen_trace_spread.py [--check] [--jobs 8] [--only fp64|fp32]
+        (--check: regenerate both and compare with the committed files instead of writing them)
 """
 import argparse
 import multiprocessing as mp
@@ -57,17 +63,33 @@ def job(args):
                          dev_abs=dev_abs, dev_rel=dev_rel)
 
 
-def generate(jobs):
-    todo = [(n, b) for n in tc.CASES for b in (0, 1)]
+def job32(args):
+    """The fp32 fixture's part of one (case, scenario): the refined float32 variants against the
+    plain fp64 oracle."""
+    name, b = args
+    try:
+        from threadpoolctl import threadpool_limits
+        threadpool_limits(1)
+    except ImportError:
+        pass
+    case = tc.build_case(name)
+    plain = tc.oracle_trace(case, b)
+    variants = [tc.oracle_trace(case, b, v)[:2] for v in tc.FP32_VARIANTS]
+    lead, dev_abs, dev_rel = tc.spread(plain[:2], variants)
+    return name, b, dict(lead=np.int32(lead), dev_abs=dev_abs, dev_rel=dev_rel)
+
+
+def generate(jobs, fp32=False):
+    todo = [(n, b) for n in (tc.GATED if fp32 else tc.CASES) for b in (0, 1)]
     out = {"fields": np.array(tc.FIELDS)}
     with mp.get_context("fork").Pool(jobs) as pool:
-        for name, b, r in pool.imap_unordered(job, todo):
+        for name, b, r in pool.imap_unordered(job32 if fp32 else job, todo):
             for k, v in r.items():
                 if k.startswith("dev_"):  # per case: the larger of the two scenarios'
                     out[f"{name}__{k}"] = np.maximum(out.get(f"{name}__{k}", 0.0), v)
                 else:
                     out[f"{name}__{b}__{k}"] = v
-            print(f"{name}/{b}: lead {int(r['lead'])}, status {int(r['status'])}, largest relative deviation "
+            print(f"{name}/{b}{' fp32' if fp32 else ''}: lead {int(r['lead'])}, largest relative deviation "
                   + ", ".join(f"{f} {r['dev_rel'][i]:.1e}" for i, f in enumerate(tc.FIELDS)), flush=True)
     return dict(sorted(out.items()))
 
@@ -76,16 +98,23 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--jobs", type=int, default=8)
+    ap.add_argument("--only", choices=("fp64", "fp32"), help="one of the two fixtures (default: both)")
     a = ap.parse_args()
-    out = generate(a.jobs)
-    if a.check:
-        old = np.load(tc.FIXTURE)
-        assert sorted(old.files) == sorted(out), "key sets differ"
-        bad = [k for k in out if not np.array_equal(old[k], out[k], equal_nan=k.endswith(("rows", "chk")))]
-        print("fixture reproduced bit for bit" if not bad else f"DIFFERENT: {bad}")
-        sys.exit(1 if bad else 0)
-    np.savez_compressed(tc.FIXTURE, **out)
-    print(f"wrote {tc.FIXTURE} ({os.path.getsize(tc.FIXTURE)} bytes)")
+    rc = 0
+    for path, fp32 in ((tc.FIXTURE, False), (tc.FIXTURE_FP32, True)):
+        if a.only and a.only != ("fp32" if fp32 else "fp64"):
+            continue
+        out = generate(a.jobs, fp32)
+        if a.check:
+            old = np.load(path)
+            assert sorted(old.files) == sorted(out), "key sets differ"
+            bad = [k for k in out if not np.array_equal(old[k], out[k], equal_nan=k.endswith(("rows", "chk")))]
+            print(f"{os.path.basename(path)}: " + ("fixture reproduced bit for bit" if not bad else f"DIFFERENT: {bad}"))
+            rc |= 1 if bad else 0
+        else:
+            np.savez_compressed(path, **out)
+            print(f"wrote {path} ({os.path.getsize(path)} bytes)")
+    sys.exit(rc)
 
 
 if __name__ == "__main__":

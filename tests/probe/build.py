@@ -18,7 +18,10 @@ LIB = os.path.join(OUT_DIR, "libnmpc_probe.so")
 STAMP = LIB + ".hash"
 
 EXPORTS = ("nmpc_probe_wreduce", "nmpc_probe_readlane_f64", "nmpc_probe_readlane_f32", "nmpc_probe_logacc",
-           "nmpc_probe_unary", "nmpc_probe_rsqf", "nmpc_probe_qd")
+           "nmpc_probe_unary", "nmpc_probe_rsqf", "nmpc_probe_qd", "nmpc_probe_lq_step")
+# nmpc_probe_lq_step's cls argument: the kernel class whose factorisation, solves and refinement run
+LQ_CLASSES = {"C": 0, "C32": 1, "A32": 2}
+LQ_CAPACITY = {"C": (63, 21), "C32": (63, 21), "A32": (20, 15)}  # N, rows per stage
 
 
 def _entry():
@@ -32,7 +35,9 @@ def _entry():
 def probe_hash() -> str:
     ge = _entry()
     h = hashlib.sha256()
-    for f in (SRC, os.path.join(ge.CSRC, "nmpc_solve.hip"), os.path.join(ROOT, "include", "nmpc_amd.h")):
+    # every file the probe's translation unit reads: nmpc_solve.hip includes nmpc_eval.h
+    for f in (SRC, os.path.join(ge.CSRC, "nmpc_solve.hip"), os.path.join(ge.CSRC, "nmpc_eval.h"),
+              os.path.join(ROOT, "include", "nmpc_amd.h")):
         with open(f, "rb") as fh:
             h.update(fh.read())
     h.update(" ".join(ge._flags()).replace(ROOT, "").encode())
@@ -73,6 +78,7 @@ def lib():
     L.nmpc_probe_unary.argtypes = [i32, i64, dp, dp]
     L.nmpc_probe_rsqf.argtypes = [i64, fp, fp]
     L.nmpc_probe_qd.argtypes = [i64, dp, dp, dp]
+    L.nmpc_probe_lq_step.argtypes = ([i32, C.c_void_p, i32, i32, dp, dp, dp, C.c_double] + [dp] * 5 + [dp, dp, dp, ip])
     for n in EXPORTS:
         getattr(L, n).restype = C.c_int
     _lib = L

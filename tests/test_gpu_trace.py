@@ -6,7 +6,13 @@ the Hessian.
 Tolerances come from the oracle alone (tests/golden/trace_spread.npz, gen_trace_spread.py):
 30 x the largest deviation of the oracle's rounding variants from the plain oracle per field
 and case; mu, delta_w (1e-12) and f (1e-10) at fixed relative figures; iteration and
-line-search trial counts equal.  tests/test_oracle.py runs the same comparator on the CPU."""
+line-search trial counts equal.  tests/test_oracle.py runs the same comparator on the CPU.
+
+The fp32 classes (nlpsol option linear_solver_precision="single": A32, C32) run the same cases
+against the same plain fp64 oracle.  Their tolerance is per field the larger of the fp64 one and
+30 x the deviation of the oracle's refined float32 variants (a float32 Cholesky factor with one
+fp64 refinement step; tests/golden/trace_spread_fp32.npz), mu and delta_w still 1e-12, counts
+equal; the oracle with an UNREFINED float32 step is the reference the kernel must miss."""
 import numpy as np
 import pytest
 
@@ -20,17 +26,24 @@ def fix():
     return np.load(tc.FIXTURE)
 
 
+@pytest.fixture(scope="module")
+def fix32():
+    return np.load(tc.FIXTURE_FP32)
+
+
 _GPU = {}
 
 
-def _gpu_trace(name):
+def _gpu_trace(name, single=False):
     """case, per scenario (rows, chk) in oracle_trace's form, the solver's kernel_info"""
-    if name not in _GPU:
+    key = (name, "single") if single else name
+    if key not in _GPU:
         from nmpc_amd import nlpsol, REFERENCE_OPTS
         case = tc.build_case(name)
         spec = case["spec"]
         lbx, ubx, lbg, ubg = case["bounds"][0]
-        s = nlpsol("solver", "ipopt", spec, REFERENCE_OPTS)
+        s = nlpsol("solver", "ipopt", spec, dict(REFERENCE_OPTS, linear_solver_precision="single") if single
+                   else REFERENCE_OPTS)
         s.set_trace(True)
         s(x0=np.zeros(spec.nw), lbx=lbx, ubx=ubx, lbg=lbg, ubg=ubg, p=case["P"].T)
         tr = s.read_trace(2)
@@ -43,8 +56,8 @@ def _gpu_trace(name):
             rows[n:] = np.nan
             chk[n + 1:] = np.nan
             out.append((rows, chk))
-        _GPU[name] = (case, out, s.kernel_info())
-    return _GPU[name]
+        _GPU[key] = (case, out, s.kernel_info())
+    return _GPU[key]
 
 
 @pytest.mark.parametrize("name", tc.GATED)
@@ -77,9 +90,44 @@ def test_a_1e7_error_in_the_oracle_fails_the_comparison(fix, name):
         assert max(r for _, r in worst.values()) >= tc.MARGIN, (mut, worst)
 
 
+@pytest.mark.parametrize("name", tc.GATED)
+def test_fp32_first_iterations_match_the_oracle_within_the_refined_float32_spread(fix, fix32, name):
+    """linear_solver_precision="single" at REFERENCE_OPTS: the kernel's trace against the plain
+    fp64 oracle within the fp32 tolerance, iteration and trial counts equal on the leading
+    iterations.  Measured on an MI355X: DESIGN.md 'fp32 leg: what is tested'."""
+    _, traces, _ = _gpu_trace(name, single=True)
+    bad = []
+    for b, (rows, chk) in enumerate(traces):
+        lead, ratios = tc.compare(fix, name, b, rows, chk, fix32=fix32)
+        print(f"{name}/{b} fp32: {lead} iterations; deviation / tolerance " +
+              ", ".join(f"{k} {v:.3g}" for k, v in ratios.items()))
+        assert lead >= tc.FP32_MIN_LEAD
+        bad += [(b, k, v) for k, v in ratios.items() if not v <= 1.0]
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("name", tc.GATED)
+def test_fp32_trace_misses_the_unrefined_float32_oracle(fix, fix32, name):
+    """The fp32 kernel's trace against the oracle whose Newton step is the float32 factor's with
+    NO refinement: it must miss the fp32 tolerance on some field of the case by at least 10 x --
+    the kernel refines, and the comparison can tell."""
+    case, traces, _ = _gpu_trace(name, single=True)
+    worst = {}
+    for b, (rows, chk) in enumerate(traces):
+        ratios = tc.compare(fix, name, b, rows, chk, ref=tc.unrefined_trace(name, case, b), fix32=fix32)[1]
+        f = max(ratios, key=ratios.get)
+        worst[b] = (f, ratios[f])
+    print(f"{name} fp32 kernel against the unrefined float32 oracle: {worst}")
+    assert max(r for _, r in worst.values()) >= tc.MARGIN, worst
+
+
 def test_the_cases_run_the_intended_kernel_classes():
     """As far as the API tells: nmpc_kernel_info's LDS size is the class's layout size, so all
-    class-A cases report one size and the A, B, C and D cases four different ones."""
+    class-A cases report one size and the A, B, C and D cases four different ones.  With
+    linear_solver_precision="single" there are two sizes: A32 for the cases of class A (at most
+    a quarter CU as well) and C32 for every other one, each different from its fp64 counterpart
+    (the refinement classes keep a state step more in LDS, and A32 its trial rows in global
+    memory)."""
     lds = {n: _gpu_trace(n)[2]["lds_bytes"] for n in tc.GATED}
     print(lds)
     by_class = {}
@@ -87,7 +135,17 @@ def test_the_cases_run_the_intended_kernel_classes():
         by_class.setdefault(c, set()).add(lds[n])
     assert all(len(v) == 1 for v in by_class.values()), by_class
     assert len({next(iter(v)) for v in by_class.values()}) == 4, by_class
-    assert by_class["A"].pop() <= 40960  # the LDS-row class: a quarter CU
+    a64 = by_class["A"].pop()
+    assert a64 <= 40960  # the LDS-row class: a quarter CU
+    lds32 = {n: _gpu_trace(n, single=True)[2]["lds_bytes"] for n in tc.GATED}
+    print(lds32)
+    by32 = {}
+    for n, c in tc.CLASS_OF.items():
+        by32.setdefault("A32" if c == "A" else "C32", set()).add(lds32[n])
+    assert all(len(v) == 1 for v in by32.values()), by32
+    a32, c32 = by32["A32"].pop(), by32["C32"].pop()
+    assert a32 != c32 and a32 <= 40960
+    assert a32 != a64 and c32 != by_class["C"].pop(), (a32, a64, c32)
 
 
 def test_start_over_the_target_is_invalid_number_and_neighbours_are_unaffected():

@@ -320,3 +320,32 @@ def test_trace_comparator_passes_rounding_variants_and_catches_1e7_errors(name):
             worst[b] = (f, ratios[f])
         print(f"{name} {mut}: {worst}")
         assert max(r for _, r in worst.values()) >= tc.MARGIN, (mut, worst)
+
+
+# ---- the fp32 leg's comparator (tests/golden/trace_spread_fp32.npz): the CPU half of
+# tests/test_gpu_trace.py's linear_solver_precision="single" tests
+@pytest.mark.parametrize("name", list(__import__("tests.trace_cases", fromlist=["CASES"]).GATED))
+def test_fp32_trace_comparator_passes_refined_variants_and_catches_a_missing_refinement(name):
+    """Under the comparator the fp32 kernel classes' trace is held to, (a) every refined
+    float32 variant of the oracle (float32 Cholesky factor, one fp64 refinement step; identity
+    and three permutations, also with the literal objective) passes against the plain fp64
+    oracle on at least 4 leading iterations, and (b) the oracle with the float32 factor and NO
+    refinement misses the tolerance on some field of the case by at least 10 x."""
+    from tests import trace_cases as tc
+    fix, fix32 = np.load(tc.FIXTURE), np.load(tc.FIXTURE_FP32)
+    case = tc.build_case(name)
+    worst = {}
+    for b in (0, 1):
+        lead32 = int(fix32[f"{name}__{b}__lead"])
+        print(f"{name}/{b}: lead {lead32} (fp64 fixture {int(fix[f'{name}__{b}__lead'])})")
+        assert lead32 >= tc.FP32_MIN_LEAD, "too few comparable iterations"
+        for v in tc.FP32_VARIANTS:
+            vr, vc = tc.oracle_trace(case, b, v)[:2]
+            lead, ratios = tc.compare(fix, name, b, vr, vc, fix32=fix32)
+            print(f"{name}/{b} variant {v}: deviation / fp32 tolerance " + ", ".join(f"{k} {r:.3g}" for k, r in ratios.items()))
+            assert lead >= tc.FP32_MIN_LEAD and max(ratios.values()) <= 1.0, (b, v, ratios)
+        ratios = tc.compare(fix, name, b, *tc.unrefined_trace(name, case, b), fix32=fix32)[1]
+        f = max(ratios, key=ratios.get)
+        worst[b] = (f, ratios[f])
+    print(f"{name} unrefined float32 step: {worst}")
+    assert max(r for _, r in worst.values()) >= tc.MARGIN, worst

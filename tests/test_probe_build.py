@@ -3,6 +3,7 @@ exports its launchers, is built from the product's own kernel source, and stays 
 product (its library, and the hash nmpc_build_id reports)."""
 import ctypes
 import os
+import shutil
 import subprocess
 
 import __graft_entry__ as ge
@@ -23,6 +24,44 @@ def test_probe_cross_compiles_and_exports_its_launchers():
     assert b"nmpc_solve_batch" not in blob         # NMPC_TU_CLASS == 0: no C-ABI in the probe
     # argument validation happens before any device call
     assert pb.lib().nmpc_probe_qd(0, None, None, None) != 0
+
+
+def test_probe_exports_the_step_launcher_for_every_precision_class(tmp_path, monkeypatch):
+    """nmpc_probe_lq_step: exported, its kernel instantiated for CapC (fp64), CapC32 and CapA32
+    (fp32 factors; the mangled Cap<N, m, lds_rows, type> of each is in the device code), its
+    arguments checked before any device call, and the probe's hash covers every product file its
+    translation unit reads."""
+    path = pb.build()
+    assert "nmpc_probe_lq_step" in pb.EXPORTS and hasattr(ctypes.CDLL(path), "nmpc_probe_lq_step")
+    with open(path, "rb") as fh:
+        blob = fh.read()
+    for cap in (b"3CapILi63ELi21ELb0EdLb0EE", b"3CapILi63ELi21ELb0EfLb0EE", b"3CapILi20ELi15ELb1EfLb0EE"):
+        assert b"probe_lq_kernelIN9nmpc_impl" + cap in blob, cap
+    assert set(pb.LQ_CLASSES) == set(pb.LQ_CAPACITY) == {"C", "C32", "A32"}
+    L = pb.lib()
+    z = (ctypes.c_double * 8)()
+    q = ctypes.cast(z, ctypes.POINTER(ctypes.c_double))
+    i = ctypes.cast((ctypes.c_int32 * 2)(), ctypes.POINTER(ctypes.c_int32))
+    assert L.nmpc_probe_lq_step(0, None, 1, 1, q, q, q, 1.0, q, q, q, q, q, q, q, q, i) == 1    # no description
+    from nmpc_amd import _lib
+    d = _lib.Desc()                                                                           # N = 0: refused
+    assert L.nmpc_probe_lq_step(0, ctypes.byref(d), 1, 1, q, q, q, 1.0, q, q, q, q, q, q, q, q, i) == 1
+    d.N, d.np, d.T = 21, 11, 0.2
+    assert L.nmpc_probe_lq_step(7, ctypes.byref(d), 1, 1, q, q, q, 1.0, q, q, q, q, q, q, q, q, i) == 1  # no such class
+    assert L.nmpc_probe_lq_step(2, ctypes.byref(d), 1, 1, q, q, q, 1.0, q, q, q, q, q, q, q, q, i) == 1  # N > 20 in CapA32
+    assert L.nmpc_probe_lq_step(0, ctypes.byref(d), 0, 1, q, q, q, 1.0, q, q, q, q, q, q, q, q, i) == 1  # B = 0
+    assert list(z) == [0.0] * 8
+    copy = tmp_path / "csrc"
+    shutil.copytree(ge.CSRC, copy)
+    before = pb.probe_hash()
+    monkeypatch.setattr(ge, "CSRC", str(copy))
+    assert pb.probe_hash() == before
+    for f in ("nmpc_solve.hip", "nmpc_eval.h"):
+        with open(copy / f, "ab") as fh:
+            fh.write(b"\n// x\n")
+        changed = pb.probe_hash()
+        assert changed != before, f
+        before = changed
 
 
 def test_probe_includes_the_product_source_and_the_product_ignores_the_probe():

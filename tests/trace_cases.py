@@ -23,6 +23,17 @@ MAX_ITER = 8
 # oracle in both ways (Riccati step; literal stage cost, butterfly sums).
 VARIANTS = ((1, 0), (2, 0), (3, 0), (0, 1), (1, 1))
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "trace_spread.npz")
+# the fp32 leg (nlpsol option linear_solver_precision="single"; kernel classes A32, C32): the
+# Newton step from a float32 Cholesky factor with one fp64 refinement step (oracle _Chol
+# variants 4..7: identity and the three permutations), also crossed with evaluation variant 1.
+# tests/golden/trace_spread_fp32.npz holds, per GATED case, their largest deviation from the
+# plain fp64 oracle per field and, per scenario, the leading iterations on which all of them
+# take the plain oracle's iteration and trial counts.  (la_variant 8, 0): the float32 factor
+# with NO refinement, the deliberately wrong reference of the fp32 tests.
+FP32_VARIANTS = ((4, 0), (5, 0), (6, 0), (7, 0), (4, 1))
+FP32_UNREFINED = (8, 0)
+FIXTURE_FP32 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "trace_spread_fp32.npz")
+FP32_MIN_LEAD = 4
 
 # trace row fields (include/nmpc_amd.h: columns 1..6 of a trace row) and the convergence
 # check's (columns 8..11 of the row of the same iteration count)
@@ -152,16 +163,22 @@ def field_values(rows, chk, lead):
     return out
 
 
-def compare(fix, name, b, rows, chk, ref=None):
+def compare(fix, name, b, rows, chk, ref=None, fix32=None):
     """Compare a trace (rows, chk as oracle_trace returns them) with the fixture's plain
     oracle -- or with `ref` = (rows, chk) of another reference, e.g. a deliberately wrong
     oracle -- under the fixture's tolerances.  -> (lead, {field: worst deviation / tolerance});
     iter / ls mismatches are reported as field 'ls' with ratio inf.  mu, delta and f: the
     fixed figures of FIXED_REL.  Every other field: FACTOR x the variants' largest relative
     deviation on the case, or, for theta and the check fields where the reference value is
-    below SMALL, FACTOR x their largest absolute deviation."""
+    below SMALL, FACTOR x their largest absolute deviation.
+    fix32 (the fp32 fixture): the fp32 leg's comparison -- per field the larger of that
+    tolerance and FACTOR x the refined float32 variants' deviation (f: the larger of its fixed
+    figure and that; mu and delta keep their fixed 1e-12), on the leading iterations both
+    fixtures vouch for."""
     key = f"{name}__{b}"
     lead = int(fix[key + "__lead"])
+    if fix32 is not None:
+        lead = min(lead, int(fix32[key + "__lead"]))
     prow, pchk = (fix[key + "__rows"], fix[key + "__chk"]) if ref is None else ref
     ratios = {}
     same = np.array_equal(rows[:lead, 0], prow[:lead, 0]) and np.array_equal(rows[:lead, 7], prow[:lead, 7])
@@ -176,10 +193,15 @@ def compare(fix, name, b, rows, chk, ref=None):
         ref, g = ref[ok], g[ok]
         if f in FIXED_REL:
             tol = FIXED_REL[f] * np.abs(ref)
+            if fix32 is not None and f == "f":  # the step's error reaches f: the larger of the two
+                tol = max(FIXED_REL[f], FACTOR * fix32[name + "__dev_rel"][i]) * np.abs(ref)
         else:
-            tol = FACTOR * fix[name + "__dev_rel"][i] * np.abs(ref)
+            dev_rel, dev_abs = fix[name + "__dev_rel"][i], fix[name + "__dev_abs"][i]
+            if fix32 is not None:
+                dev_rel, dev_abs = max(dev_rel, fix32[name + "__dev_rel"][i]), max(dev_abs, fix32[name + "__dev_abs"][i])
+            tol = FACTOR * dev_rel * np.abs(ref)
             if f in ABS_BELOW:
-                tol = np.where(np.abs(ref) < SMALL, FACTOR * fix[name + "__dev_abs"][i], tol)
+                tol = np.where(np.abs(ref) < SMALL, FACTOR * dev_abs, tol)
         d = np.abs(g - ref)
         with np.errstate(divide="ignore", invalid="ignore"):
             r = np.where(d == 0, 0.0, d / tol)
@@ -278,6 +300,14 @@ def applies(mutation, case):
 
 
 _MUT_CACHE = {}
+
+
+def unrefined_trace(name, case, b):
+    """(rows, chk) of the oracle whose Newton step is the float32 factor's, unrefined."""
+    k = (name, b, "unrefined32")
+    if k not in _MUT_CACHE:
+        _MUT_CACHE[k] = oracle_trace(case, b, FP32_UNREFINED)[:2]
+    return _MUT_CACHE[k]
 
 
 def mutated_trace(name, case, b, mutation):
