@@ -413,6 +413,72 @@ int nmpc_adjoint_products_batch(nmpc_handle* h, int32_t B, int32_t na,
                                 const double* Xb, int64_t ld_Xb,
                                 double* wbar_out, double* pbar_out);
 
+/* Reverse-mode sensitivity of a SOLUTION, for a whole batch, in one launch: what a backward pass
+ * through the solve needs, with nothing on the host.  At a solve's x* (x), its multipliers
+ * lam_g*, lam_x* (CasADi's signs: negative towards the lower bound) and parameters p, with
+ * L = f + lam_g^T g, W = grad^2_w L, J = dg/dw, and the barrier weights of the point
+ *   sigma = max(-lam, 0) / max(v - lo, eps_lo) + max(lam, 0) / max(hi - v, eps_hi),
+ *   eps_b = bound_relax_factor max(1, |b|)   (the handle's option),
+ * Sigma_x from (x, lam_x, lbx, ubx) and Sigma_s from (g, lam_g, lbg, ubg), the condensed matrix
+ *   M = W + diag(Sigma_x) + delta I + J^T diag(Sigma_s + delta) J
+ * is factorised once per scenario, at delta = 0 where its inertia is right and otherwise along
+ * IPOPT's inertia-correction ladder (first_hessian_perturbation, then x perturb_inc_fact_first,
+ * then x perturb_inc_fact, while <= max_hessian_perturbation; the handle's options).  For each of
+ * na >= 1 seeds (x_bar_d on x*, lam_g_bar_d on lam_g*, X_bar_d on the state trajectory X*):
+ *   q_out    (nw na x B) = M^-1 (x_bar_d + (dX/dw)^T X_bar_d + J^T Sigma_s lam_g_bar_d)
+ *   jq_out   (ng na x B) = J q; stage 0's rows are exactly 0
+ *   pbar_out (np na x B) = -(d_p grad_w L)^T q + (dg/dp)^T Sigma_s (lam_g_bar_d - J q)
+ *                          + (dX/dp)^T X_bar_d
+ * so that <pbar, dp> = <x_bar, dx*> + <lam_g_bar, dlam_g*> + <X_bar, dX*> for every direction dp
+ * of the parameters, with (dx*, dlam_g*) the interior-point linearisation of the optimality
+ * conditions at the point.  info_out (B): 0 = factorised with the right inertia; 1 = no rung of
+ * the ladder did; -11 = an equality row (lbg == ubg, which needs the augmented system), lbx > ubx,
+ * or a weight that is not a finite non-negative number (a NaN multiplier).  With 1 or -11 the
+ * scenario's pbar, q and jq are NaN and its neighbours are untouched.  delta_out (B): the delta
+ * of the last factorisation tried (0 with -11).
+ * g is the row values the weights are taken at (a solve's g_out); NULL = the kernel's own
+ * g(x, p).  A variable with lbx == ubx is fixed: it leaves the system, its x_bar is ignored
+ * and its q is exactly 0.  A bound beyond +-1e19 enters the formula as it stands: its slack is of
+ * that size and its term vanishes to rounding.  An entry of p that nothing reads gives exactly 0
+ * in pbar_out.
+ * Within a scenario seed d occupies [d n, (d+1) n) of each seed and output array; X_bar is
+ * nx(N+1) na in X_out's layout.  Each seed may be NULL and then contributes nothing, at least one
+ * must not be.  x, p, lam_g, lam_x, g and the bounds are n per scenario with a leading dimension
+ * of their own; 0 shares one vector (or one set of seeds) with every scenario.  pbar_out or
+ * q_out must be given; jq_out, info_out and delta_out may be NULL.  Seeds are independent of each
+ * other: a non-finite entry of one seed gives non-finite output for that seed only.  The
+ * no-gimbal model has nx = 5 and nw = 3N.
+ * DEVICE pointers, enqueued on `stream`; never synchronises, and allocates nothing once the
+ * handle's workspace covers B (a solve's workspace does).  One wavefront per scenario forms
+ * every seed: the factorisation is done once.
+ * A NULL handle, B <= 0, na <= 0, a NULL x, p, lam_g, lam_x, lbx, ubx, lbg or ubg, every seed
+ * NULL, pbar_out and q_out both NULL, or a leading dimension that is neither 0 nor >= the vector
+ * length (nw na, ng na, nx(N+1) na for the seeds) return NMPC_E_INVALID before any device call. */
+int nmpc_solve_adjoint_batch_dev(nmpc_handle* h, int32_t B, int32_t na,
+                                 const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                                 const double* lam_g, int64_t ld_lam_g, const double* lam_x, int64_t ld_lam_x,
+                                 const double* g, int64_t ld_g,
+                                 const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx,
+                                 const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg,
+                                 const double* x_bar, int64_t ld_x_bar,
+                                 const double* lam_g_bar, int64_t ld_lam_g_bar,
+                                 const double* X_bar, int64_t ld_X_bar,
+                                 double* pbar_out, double* q_out, double* jq_out, int32_t* info_out,
+                                 double* delta_out, void* stream);
+
+/* Same with HOST pointers; synchronous (staged through the handle's device buffer). */
+int nmpc_solve_adjoint_batch(nmpc_handle* h, int32_t B, int32_t na,
+                             const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                             const double* lam_g, int64_t ld_lam_g, const double* lam_x, int64_t ld_lam_x,
+                             const double* g, int64_t ld_g,
+                             const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx,
+                             const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg,
+                             const double* x_bar, int64_t ld_x_bar,
+                             const double* lam_g_bar, int64_t ld_lam_g_bar,
+                             const double* X_bar, int64_t ld_X_bar,
+                             double* pbar_out, double* q_out, double* jq_out, int32_t* info_out,
+                             double* delta_out);
+
 /* Optional per-iteration trace (debugging / parity): when enabled, the next
  * solve records NMPC_TRACE_FIELDS doubles per iteration per scenario into a
  * device buffer readable with nmpc_read_trace (host pointer,

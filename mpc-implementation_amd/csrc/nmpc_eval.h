@@ -128,7 +128,38 @@ struct AdjIO {
 // (static_assert in nmpc_adjoint.hip).
 constexpr int kAdjWs = kPprodWs;
 
+// DEVICE pointers, layouts and leading dimensions as nmpc_solve_adjoint_batch_dev
+// (include/nmpc_amd.h); x, p, lam_g, lam_x and the four bounds are required, one of the seeds
+// x_bar / lam_g_bar / X_bar and one of pbar / q
+struct SadjIO {
+  const double *x, *p, *lam_g, *lam_x, *g, *lbx, *ubx, *lbg, *ubg, *x_bar, *lam_g_bar, *X_bar;
+  long long ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_x_bar, ld_lam_g_bar, ld_X_bar;
+  int na;
+  double *pbar, *q, *jq;
+  int* info;
+  double* delta;
+  double* ws;  // B x kSadjWs doubles of the handle's workspace
+};
+
+// Per-scenario workspace of the fused reverse-mode sensitivity kernel (nmpc_solve_adjoint.hip):
+// the KKT kernel's slices, used the same way (the gradient slice also holds each seed's stage
+// sources, as in the adjoint-products kernel), the row weights sigma_s and one seed's row seed
+// y = sigma_s (lam_g_bar - J q).  The unit-weight stage-cost gradients that serve a cost weight
+// taken from p (6 + 6 per stage) take the stage summaries' slice once the factorisation stands.
+// The per-obstacle curvature lam_{k,o} Hg_o of the
+// adjoint-products kernel is recomputed from X and the centres where a centre comes from p, so
+// the union stays within every solver class's workspace (static_assert in
+// nmpc_solve_adjoint.hip).
+constexpr int kSadjSg = kKktWs;
+constexpr int kSadjY = kSadjSg + (5 + NMPC_MAX_OBS) * kEvalStages;
+constexpr int kSadjWs = kSadjY + (5 + NMPC_MAX_OBS) * kEvalStages;
+
 }  // namespace nmpc_impl
+
+// Enqueues the fused reverse-mode solution sensitivities of B scenarios on `stream` (one
+// wavefront per scenario, every seed on it: the factorisation is done once).  Same contract as
+// nmpc_eval_launch.
+int nmpc_solve_adjoint_launch(const nmpc_impl::Params* dprm, int B, const nmpc_impl::SadjIO& io, void* stream);
 
 // Enqueues the adjoint products of B scenarios on `stream`: B x chunks wavefronts, wavefront
 // (b, c) forming scenario b's seeds c, c + chunks, ...  Same contract as nmpc_eval_launch.

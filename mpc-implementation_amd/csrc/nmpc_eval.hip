@@ -213,3 +213,6 @@ int nmpc_eval_launch(const Params* dprm, int B, const EvalIO& io, void* stream) 
 
 // the adjoint (transposed) products at given points: a fifth kernel of this unit
 #include "nmpc_adjoint.hip"
+
+// the reverse-mode sensitivity of a solution in one launch: a sixth kernel of this unit
+#include "nmpc_solve_adjoint.hip"

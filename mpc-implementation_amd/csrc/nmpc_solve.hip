@@ -6149,6 +6149,128 @@ int nmpc_adjoint_products_batch(nmpc_handle* h, int32_t B, int32_t na, const dou
   return NMPC_OK;
 }
 
+// ---- reverse-mode sensitivity of a solution in one launch (kernel: nmpc_solve_adjoint.hip)
+struct SadjArgs {
+  // x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, x_bar, lam_g_bar, X_bar
+  const double* in[12];
+  int64_t ld[12];
+  double *pbar, *q, *jq;
+  int32_t* info;
+  double* delta;
+};
+// the vector length each input's leading dimension must cover
+static void sadj_lengths(const Params& P, int32_t na, size_t vlen[12]) {
+  const size_t nw = P.nwE, ng = P.ng, np = P.npE, nX = (size_t)P.nxE * (P.N + 1);
+  const size_t v[12] = {nw, np, ng, nw, ng, nw, nw, ng, ng, nw * (size_t)na, ng * (size_t)na, nX * (size_t)na};
+  for (int i = 0; i < 12; ++i) vlen[i] = v[i];
+}
+// the argument checks of both entry points: nothing here touches the device
+static int sadj_check(const nmpc_handle* h, int32_t B, int32_t na, const SadjArgs& a) {
+  if (!h) return fail(NMPC_E_INVALID, "null handle");
+  if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
+  if (na <= 0) return fail(NMPC_E_INVALID, "na <= 0");
+  for (int i = 0; i < 9; ++i)
+    if (i != 4 && !a.in[i])
+      return fail(NMPC_E_INVALID, "required pointer is null (x, p, lam_g, lam_x, lbx, ubx, lbg, ubg)");
+  if (!a.in[9] && !a.in[10] && !a.in[11])
+    return fail(NMPC_E_INVALID, "every seed pointer is null (x_bar, lam_g_bar, X_bar)");
+  if (!a.pbar && !a.q) return fail(NMPC_E_INVALID, "both pbar_out and q_out are null");
+  size_t vlen[12];
+  sadj_lengths(h->hp, na, vlen);
+  for (int i = 0; i < 12; ++i)
+    if (a.in[i] && a.ld[i] != 0 && a.ld[i] < (int64_t)vlen[i])
+      return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
+  return NMPC_OK;
+}
+// checked arguments, DEVICE pointers: workspace from the handle (sized like a solve's, grown
+// only when it does not cover B yet), then one launch
+static int sadj_enqueue(nmpc_handle* h, int32_t B, int32_t na, const SadjArgs& a, void* stream) {
+  const int per = h->ws_doubles > kSadjWs ? h->ws_doubles : kSadjWs;
+  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
+  SadjIO io;
+  io.x = a.in[0]; io.p = a.in[1]; io.lam_g = a.in[2]; io.lam_x = a.in[3]; io.g = a.in[4];
+  io.lbx = a.in[5]; io.ubx = a.in[6]; io.lbg = a.in[7]; io.ubg = a.in[8];
+  io.x_bar = a.in[9]; io.lam_g_bar = a.in[10]; io.X_bar = a.in[11];
+  io.ld_x = a.ld[0]; io.ld_p = a.ld[1]; io.ld_lam_g = a.ld[2]; io.ld_lam_x = a.ld[3]; io.ld_g = a.ld[4];
+  io.ld_lbx = a.ld[5]; io.ld_ubx = a.ld[6]; io.ld_lbg = a.ld[7]; io.ld_ubg = a.ld[8];
+  io.ld_x_bar = a.ld[9]; io.ld_lam_g_bar = a.ld[10]; io.ld_X_bar = a.ld[11];
+  io.na = na;
+  io.pbar = a.pbar; io.q = a.q; io.jq = a.jq; io.info = a.info; io.delta = a.delta;
+  io.ws = h->dws;
+  const hipError_t e = (hipError_t)nmpc_solve_adjoint_launch(h->dprm, (int)B, io, stream);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("solve adjoint launch: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
+int nmpc_solve_adjoint_batch_dev(nmpc_handle* h, int32_t B, int32_t na, const double* x, int64_t ld_x,
+                                 const double* p, int64_t ld_p, const double* lam_g, int64_t ld_lam_g,
+                                 const double* lam_x, int64_t ld_lam_x, const double* g, int64_t ld_g,
+                                 const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx,
+                                 const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg,
+                                 const double* x_bar, int64_t ld_x_bar, const double* lam_g_bar,
+                                 int64_t ld_lam_g_bar, const double* X_bar, int64_t ld_X_bar, double* pbar_out,
+                                 double* q_out, double* jq_out, int32_t* info_out, double* delta_out, void* stream) {
+  const SadjArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, x_bar, lam_g_bar, X_bar},
+                   {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_x_bar, ld_lam_g_bar,
+                    ld_X_bar},
+                   pbar_out, q_out, jq_out, info_out, delta_out};
+  if (int rc = sadj_check(h, B, na, a)) return rc;
+  return sadj_enqueue(h, B, na, a, stream);
+}
+
+int nmpc_solve_adjoint_batch(nmpc_handle* h, int32_t B, int32_t na, const double* x, int64_t ld_x, const double* p,
+                             int64_t ld_p, const double* lam_g, int64_t ld_lam_g, const double* lam_x,
+                             int64_t ld_lam_x, const double* g, int64_t ld_g, const double* lbx, int64_t ld_lbx,
+                             const double* ubx, int64_t ld_ubx, const double* lbg, int64_t ld_lbg,
+                             const double* ubg, int64_t ld_ubg, const double* x_bar, int64_t ld_x_bar,
+                             const double* lam_g_bar, int64_t ld_lam_g_bar, const double* X_bar, int64_t ld_X_bar,
+                             double* pbar_out, double* q_out, double* jq_out, int32_t* info_out,
+                             double* delta_out) {
+  const SadjArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, x_bar, lam_g_bar, X_bar},
+                   {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_x_bar, ld_lam_g_bar,
+                    ld_X_bar},
+                   pbar_out, q_out, jq_out, info_out, delta_out};
+  if (int rc = sadj_check(h, B, na, a)) return rc;
+  const Params& P = h->hp;
+  // staging: the twelve inputs (absent ones take no room), the three outputs, delta, the verdicts
+  size_t vlen[12], n_in[12], total = 0;
+  sadj_lengths(P, na, vlen);
+  double* hout[4] = {pbar_out, q_out, jq_out, delta_out};
+  const size_t olen[4] = {(size_t)P.npE * na, (size_t)P.nwE * na, (size_t)P.ng * na, 1};
+  for (int i = 0; i < 12; ++i) {
+    n_in[i] = !a.in[i] ? 0 : (a.ld[i] == 0 ? vlen[i] : (size_t)(B - 1) * (size_t)a.ld[i] + vlen[i]);
+    total += n_in[i];
+  }
+  for (int i = 0; i < 4; ++i) total += hout[i] ? (size_t)B * olen[i] : 0;
+  total += info_out ? ((size_t)B + 1) / 2 : 0;  // B int32 in whole doubles
+  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
+  double* q = h->dbuf;
+  SadjArgs d = a;
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 12; ++i) {
+    d.in[i] = a.in[i] ? q : nullptr;
+    if (a.in[i] && e == hipSuccess) e = hipMemcpy(q, a.in[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
+    q += n_in[i];
+  }
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
+  double* dout[4];
+  for (int i = 0; i < 4; ++i) {
+    dout[i] = hout[i] ? q : nullptr;
+    q += hout[i] ? (size_t)B * olen[i] : 0;
+  }
+  d.pbar = dout[0]; d.q = dout[1]; d.jq = dout[2]; d.delta = dout[3];
+  d.info = info_out ? (int32_t*)q : nullptr;
+  if (int rc = sadj_enqueue(h, B, na, d, nullptr)) return rc;
+  e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
+  for (int i = 0; i < 4; ++i)
+    if (hout[i] && e == hipSuccess)
+      e = hipMemcpy(hout[i], dout[i], (size_t)B * olen[i] * sizeof(double), hipMemcpyDeviceToHost);
+  if (info_out && e == hipSuccess) e = hipMemcpy(info_out, d.info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
 int nmpc_shift_dev(nmpc_handle* h, int32_t B, double* p, int64_t ld_p, const double* u_sol, double* w_out,
                    const double* v_t, const double* w_t, void* stream) {
   if (!h) return fail(NMPC_E_INVALID, "null handle");

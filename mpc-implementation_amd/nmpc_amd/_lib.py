@@ -30,6 +30,7 @@ EXPORTS = (
     "nmpc_kkt_solve_batch", "nmpc_kkt_solve_batch_dev",
     "nmpc_param_products_batch", "nmpc_param_products_batch_dev",
     "nmpc_adjoint_products_batch", "nmpc_adjoint_products_batch_dev",
+    "nmpc_solve_adjoint_batch", "nmpc_solve_adjoint_batch_dev",
 )
 
 _OPT_INT = ("max_iter", "acceptable_iter", "max_soc", "max_soft_resto_iters",
@@ -122,6 +123,9 @@ def lib():
                                                   + [dp, i64] * 3 + [dp] * 2)
         L.nmpc_adjoint_products_batch_dev.argtypes = ([vp, C.c_int32, C.c_int32] + [vp, i64] * 3 + [C.c_double]
                                                       + [vp, i64] * 3 + [vp] * 2 + [vp])
+    if hasattr(L, "nmpc_solve_adjoint_batch") or not os.environ.get("NMPC_LIB"):
+        L.nmpc_solve_adjoint_batch.argtypes = [vp, C.c_int32, C.c_int32] + [dp, i64] * 12 + [dp] * 3 + [i32p, dp]
+        L.nmpc_solve_adjoint_batch_dev.argtypes = [vp, C.c_int32, C.c_int32] + [vp, i64] * 12 + [vp] * 5 + [vp]
     L.nmpc_set_trace.argtypes = [vp, C.c_int32]
     L.nmpc_read_trace.argtypes = [vp, C.c_int32, dp]
     L.nmpc_shift_dev.argtypes = [vp, C.c_int32, vp, i64, vp, vp, vp, vp, vp]

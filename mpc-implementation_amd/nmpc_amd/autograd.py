@@ -4,8 +4,10 @@
     loss(x, X).backward()          # p.grad: d loss / d p, every entry of p at once
 
 Forward is :meth:`Solver.solve_device`; backward is :meth:`Solver.sensitivity_adjoint` (one KKT
-solve with one right-hand side and one transposed product per scenario, whatever np is).  This
-module holds no mathematics of its own.  torch is imported lazily, as the device methods do.
+solve with one right-hand side and one transposed product per scenario, whatever np is), or with
+``backward="device"`` one :meth:`Solver.sensitivity_adjoint_device` launch that reads nothing
+back.  This module holds no mathematics of its own.  torch is imported lazily, as the device
+methods do.
 """
 from __future__ import annotations
 
@@ -22,7 +24,7 @@ def _function():
 
     class _Solve(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, p, solver, lbx, ubx, lbg, ubg, x0):
+        def forward(ctx, p, solver, lbx, ubx, lbg, ubg, x0, device):
             assert p.dtype == torch.float64 and p.is_cuda and p.dim() == 2 and p.shape[1] == solver.np, tuple(p.shape)
             B = p.shape[0]
             f64 = dict(dtype=torch.float64, device=p.device)
@@ -36,7 +38,11 @@ def _function():
                    "status": torch.empty(B, dtype=torch.int32, device=p.device)}
             solver.solve_device(w0, *dev, pd, out)
             ctx.set_materialize_grads(False)  # an output the loss does not read seeds nothing
-            ctx.solver, ctx.bounds = solver, bounds
+            ctx.solver, ctx.bounds, ctx.device = solver, bounds, device
+            if device:  # everything stays where it is: no copy, no synchronisation
+                ctx.sol = {k: out[k].detach() for k in ("x", "g", "lam_x", "lam_g")}
+                ctx.p, ctx.dev, ctx.status = pd, dev, out["status"]
+                return out["x"], out["X"]
             # the solution as sensitivity_adjoint takes it: columns per scenario, on the host
             ctx.sol = {k: out[k].cpu().numpy().T for k in ("x", "g", "lam_x", "lam_g")}
             ctx.p = pd.cpu().numpy().T
@@ -45,6 +51,18 @@ def _function():
 
         @staticmethod
         def backward(ctx, x_bar, X_bar):
+            if ctx.device:
+                ref = x_bar if x_bar is not None else X_bar
+                B, s = ctx.p.shape[0], ctx.solver
+                seeds = {k: None if t is None else t.detach().to(torch.float64).contiguous().reshape(B, 1, n)
+                         for k, t, n in (("x_bar", x_bar, s.nw), ("X_bar", X_bar, s.nX))}
+                o = {"pbar": torch.empty(B, 1, s.np, dtype=torch.float64, device=ref.device),
+                     "info": torch.empty(B, dtype=torch.int32, device=ref.device)}
+                s.sensitivity_adjoint_device(ctx.sol, *ctx.dev, ctx.p, o, **seeds)
+                ok = (o["info"] == 0) & ((ctx.status == 0) | (ctx.status == 1))
+                g = torch.where(ok[:, None], o["pbar"][:, 0, :], torch.full_like(o["pbar"][:, 0, :], float("nan")))
+                return (g,) + (None,) * 7
+
             def seed(t):  # (B, n) -> (n, 1, B)
                 return None if t is None else np.ascontiguousarray(t.detach().cpu().numpy().T[:, None, :])
 
@@ -52,17 +70,25 @@ def _function():
             g = np.ascontiguousarray(r["pbar"][:, 0, :].T)  # (B, np); NaN rows where info != 0
             g[~np.isin(ctx.status, _SUCCESS)] = np.nan
             ref = x_bar if x_bar is not None else X_bar
-            return (torch.tensor(g, dtype=torch.float64, device=ref.device),) + (None,) * 6
+            return (torch.tensor(g, dtype=torch.float64, device=ref.device),) + (None,) * 7
 
     return _Solve
 
 
-def solve(solver, p, lbx, ubx, lbg, ubg, x0=None):
+def solve(solver, p, lbx, ubx, lbg, ubg, x0=None, backward="host"):
     """Solves the batch at the parameters ``p`` -- a (B, np) float64 CUDA tensor that may require
     grad -- and returns the solution ``x`` (B, nw) and its state trajectory ``X`` (B, nx(N+1)) as
     CUDA tensors through which ``backward`` reaches p.  ``lbx``, ``ubx``, ``lbg``, ``ubg`` are
     host arrays as :meth:`Solver.__call__` takes them ((n,) or (n,B)); ``x0`` is a (B, nw) CUDA
     tensor, absent = zeros.  A scenario that did not converge (status not 0 or 1), or whose KKT
     matrix does not factorise along the delta ladder (``info`` 1), gets a NaN row in p's gradient.
-    Equality rows raise in backward, as :meth:`Solver.barrier_weights` does."""
-    return _function().apply(p, solver, lbx, ubx, lbg, ubg, x0)
+    Equality rows raise in backward, as :meth:`Solver.barrier_weights` does.
+
+    ``backward="device"`` keeps the solution, the bounds and the status on the device and runs
+    backward as one :meth:`Solver.sensitivity_adjoint_device` launch: neither pass copies to the
+    host or synchronises, so the layer can be enqueued behind other work.  The NaN rows are then
+    applied on the device, and an equality row gives a NaN row (``info`` -11) instead of raising.
+    The default ``"host"`` is the three-launch route of :meth:`Solver.sensitivity_adjoint`."""
+    if backward not in ("host", "device"):
+        raise ValueError(f"backward: expected 'host' or 'device', got {backward!r}")
+    return _function().apply(p, solver, lbx, ubx, lbg, ubg, x0, backward == "device")

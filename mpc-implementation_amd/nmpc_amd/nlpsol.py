@@ -957,6 +957,122 @@ class Solver:
         pbar[:, :, r["info"] != 0] = np.nan
         return {"pbar": pbar, "info": r["info"], "delta": delta, "q": r["dw"], "jq": r["jdw"]}
 
+    # ---- the same in one launch (nmpc_solve_adjoint_batch: weights, ladder, solves, pullback)
+    def sensitivity_adjoint_fused(self, sol: dict, lbx, ubx, lbg, ubg, p, x_bar=None, lam_g_bar=None, X_bar=None):
+        """:meth:`sensitivity_adjoint` as one kernel launch: the same arguments, the same dict
+        (``pbar`` (np,na,B), ``q`` (nw,na,B), ``jq`` (ng,na,B), ``info`` (B,), ``delta`` (B,)).
+        The barrier weights (``sol["g"]`` serves the rows when present, the kernel's own g(x, p)
+        otherwise), the delta ladder, the solves and the pullback all run on the device; the
+        host only stages the arrays.  Equality rows raise ``ValueError``, as
+        :meth:`barrier_weights` does."""
+        x, ld_x = self._arg(sol["x"], self.nw, 0.0, "x")
+        B = x.shape[0]
+        ins = [(x, ld_x)]
+        for name, a, n in (("p", p, self.np), ("lam_g", sol["lam_g"], self.ng), ("lam_x", sol["lam_x"], self.nw),
+                           ("g", sol.get("g"), self.ng), ("lbx", lbx, self.nw), ("ubx", ubx, self.nw),
+                           ("lbg", lbg, self.ng), ("ubg", ubg, self.ng)):
+            if a is None:
+                ins.append((None, 0))
+                continue
+            a, ld = self._arg(a, n, 0.0, name)
+            if ld and a.shape[0] != B:
+                raise ValueError(f"{name}: batch size {a.shape[0]} does not match {B}")
+            ins.append((a, ld))
+        na = None
+        for name, r, n in (("x_bar", x_bar, self.nw), ("lam_g_bar", lam_g_bar, self.ng), ("X_bar", X_bar, self.nX)):
+            if r is None:
+                ins.append((None, 0))
+                continue
+            a, ld, k = self._rhs(r, n, name)
+            if na not in (None, k):
+                raise ValueError(f"{name}: {k} seeds do not match {na}")
+            na = k
+            if ld and a.shape[0] != B:
+                raise ValueError(f"{name}: batch size {a.shape[0]} does not match {B}")
+            ins.append((a, ld))
+        if na is None:
+            raise ValueError("x_bar, lam_g_bar or X_bar is required")
+        out = {"pbar": np.empty((B, na, self.np)), "q": np.empty((B, na, self.nw)), "jq": np.empty((B, na, self.ng))}
+        info, delta = np.empty(B, dtype=np.int32), np.empty(B)
+        flat = []
+        for a, ld in ins:
+            flat += [_dptr(a) if a is not None else None, ld]
+        _lib.check(_lib.lib().nmpc_solve_adjoint_batch(
+            self._h, B, na, *flat, _dptr(out["pbar"]), _dptr(out["q"]), _dptr(out["jq"]),
+            info.ctypes.data_as(_IP), _dptr(delta)))
+        if np.any(info == -11):
+            lo, hi = (np.asarray(v, dtype=np.float64).reshape(self.ng, -1) for v in (lbg, ubg))
+            if np.any(lo == hi):
+                raise ValueError("sensitivity_adjoint_fused: equality rows (lbg == ubg) are not supported")
+        res = {k: np.ascontiguousarray(t.transpose(2, 1, 0)) for k, t in out.items()}
+        res["info"], res["delta"] = info, delta
+        return res
+
+    def sensitivity_adjoint_device(self, sol: dict, lbx, ubx, lbg, ubg, p, out: dict, x_bar=None, lam_g_bar=None,
+                                   X_bar=None, stream=None):
+        """Device path of :meth:`sensitivity_adjoint_fused`: torch CUDA float64 tensors.  ``sol``
+        holds x (B,nw), lam_g (B,ng), lam_x (B,nw) and optionally g (B,ng) as
+        :meth:`solve_device` leaves them; the bounds and ``p`` are scenario-major (B, n) or shared
+        (n,); each seed is (B, na, n) or shared (na, n), or None; ``out`` holds preallocated
+        device tensors, any of pbar (B,na,np), q (B,na,nw), jq (B,na,ng), info (B,) int32 and
+        delta (B,) -- pbar or q at least.  A scenario whose ``info`` is not 0 (1: no rung of the
+        delta ladder factorises; -11: an equality row, lbx > ubx or a NaN multiplier) has NaN in
+        pbar, q and jq.  Enqueued on ``stream`` (default = current); never synchronises the host
+        and reads nothing back."""
+        import torch  # plumbing only: device memory and streams
+
+        given = [out[k] for k in ("pbar", "q") if out.get(k) is not None]
+        if not given:
+            raise ValueError("sensitivity_adjoint_device: out holds neither pbar nor q")
+        if x_bar is None and lam_g_bar is None and X_bar is None:
+            raise ValueError("x_bar, lam_g_bar or X_bar is required")
+        B, na = given[0].shape[0], given[0].shape[1]
+
+        def dv(t, n, name):
+            if t is None:
+                return C.c_void_p(0), 0
+            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), name
+            if t.dim() == 1:
+                assert t.shape[0] == n, name
+                return C.c_void_p(t.data_ptr()), 0
+            assert t.shape == (B, n), (name, tuple(t.shape), (B, n))
+            return C.c_void_p(t.data_ptr()), n
+
+        def sv(t, n, name):
+            if t is None:
+                return C.c_void_p(0), 0
+            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), name
+            assert tuple(t.shape) in ((na, n), (B, na, n)), (name, tuple(t.shape))
+            return C.c_void_p(t.data_ptr()), (0 if t.dim() == 2 else na * n)
+
+        for k in ("x", "lam_g", "lam_x"):
+            if sol.get(k) is None:
+                raise ValueError(f"sol: {k} is required")
+        ins = []
+        for name, t, n in (("x", sol["x"], self.nw), ("p", p, self.np), ("lam_g", sol["lam_g"], self.ng),
+                           ("lam_x", sol["lam_x"], self.nw), ("g", sol.get("g"), self.ng), ("lbx", lbx, self.nw),
+                           ("ubx", ubx, self.nw), ("lbg", lbg, self.ng), ("ubg", ubg, self.ng)):
+            if t is None and name != "g":
+                raise ValueError(f"{name} is required")
+            ins += list(dv(t, n, name))
+        ins += (list(sv(x_bar, self.nw, "x_bar")) + list(sv(lam_g_bar, self.ng, "lam_g_bar"))
+                + list(sv(X_bar, self.nX, "X_bar")))
+        outs = []
+        for k, n in (("pbar", self.np), ("q", self.nw), ("jq", self.ng)):
+            t = out.get(k)
+            if t is not None:
+                assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B, na, n), k
+            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
+        for k, dt in (("info", torch.int32), ("delta", torch.float64)):
+            t = out.get(k)
+            if t is not None:
+                assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B,), k
+            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        _lib.check(_lib.lib().nmpc_solve_adjoint_batch_dev(self._h, B, na, *ins, *outs,
+                                                           C.c_void_p(stream.cuda_stream)))
+
     def shift_device(self, p, u_sol, w_out, v_t, w_t, stream=None):
         """Closed-loop shift on device (Python/NMPC_TT.py:13-30), see nmpc_shift_dev."""
         import torch
