@@ -479,6 +479,65 @@ int nmpc_solve_adjoint_batch(nmpc_handle* h, int32_t B, int32_t na,
                              double* pbar_out, double* q_out, double* jq_out, int32_t* info_out,
                              double* delta_out);
 
+/* Forward-mode sensitivity of a SOLUTION, for a whole batch, in one launch: the first-order change
+ * of x*, lam_g* and the state trajectory X* with the parameters -- the NMPC law's feedback gain
+ * d u0* / d x0 and the prediction x* + (dx* / dp) Dp for a changed initial state or target -- with
+ * nothing on the host.  The point (x, lam_g, lam_x, p, g and the four bounds), the barrier weights
+ * Sigma_x, Sigma_s, the condensed matrix
+ *   M = W + diag(Sigma_x) + delta I + J^T diag(Sigma_s + delta) J
+ * and its delta ladder are those of nmpc_solve_adjoint_batch_dev (above); M is factorised once
+ * per scenario.  For each of nd >= 1 directions dp_d of the parameters, with the exact parameter
+ * derivatives of nmpc_param_products_batch_dev at (x*, lam_g*), obj_factor = 1:
+ *   dx_out     (nw nd x B)      : M dx = -(d_p grad_w L) dp_d - J^T Sigma_s (dg/dp) dp_d
+ *   dlam_g_out (ng nd x B)      = Sigma_s (J dx + (dg/dp) dp_d): the sum first, then the weight;
+ *                                 stage 0's rows, where J is zero, are Sigma_s (dg/dp) dp_d
+ *   dX_out     (nx(N+1) nd x B) = (dX/dw) dx + (dX/dp) dp_d, in X_out's layout
+ * (dx*, dlam_g*) is the interior-point linearisation of the optimality conditions at the point,
+ * and <pbar, dp> = <x_bar, dx> + <lam_g_bar, dlam_g> + <X_bar, dX> holds with the pbar of
+ * nmpc_solve_adjoint_batch_dev for every seed.  info_out (B): 0 = factorised with the right
+ * inertia; 1 = no rung of the ladder did; -11 = an equality row (lbg == ubg, which needs the
+ * augmented system), lbx > ubx, or a weight that is not a finite non-negative number (a NaN
+ * multiplier).  With 1 or -11 the scenario's dx, dlam_g and dX are NaN and its neighbours are
+ * untouched.  delta_out (B): the delta of the last factorisation tried (0 with -11).
+ * g is the row values the weights are taken at (a solve's g_out); NULL = the kernel's own
+ * g(x, p).  A variable with lbx == ubx is fixed: it leaves the system and its dx is exactly 0.
+ * A direction along an entry of p that nothing reads gives dx, dlam_g and dX equal to 0 (the
+ * entry is never loaded: a NaN there changes nothing).  A bound beyond +-1e19 enters the weights'
+ * formula as it stands.
+ * Within a scenario direction d occupies [d n, (d+1) n) of dp (n = np) and of each output array.
+ * x, p, lam_g, lam_x, g and the bounds are n per scenario with a leading dimension of their own;
+ * 0 shares one vector with every scenario, and ld_dp = 0 one set of nd directions.  At least one
+ * of dx_out, dlam_g_out, dX_out must be given; the others, info_out and delta_out may be NULL.
+ * Directions are independent of each other: every per-direction buffer is rewritten by each
+ * direction, so a non-finite entry of one direction gives non-finite output for that direction
+ * only.  The no-gimbal model has nx = 5 and nw = 3N.
+ * DEVICE pointers, enqueued on `stream`; never synchronises, and allocates nothing once the
+ * handle's workspace covers B (a solve's workspace does).  One wavefront per scenario forms
+ * every direction: the factorisation is done once.
+ * A NULL handle, B <= 0, nd <= 0, a NULL x, p, lam_g, lam_x, lbx, ubx, lbg, ubg or dp, every
+ * output NULL, or a leading dimension that is neither 0 nor >= the vector length (np nd for dp)
+ * return NMPC_E_INVALID before any device call. */
+int nmpc_solve_tangent_batch_dev(nmpc_handle* h, int32_t B, int32_t nd,
+                                 const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                                 const double* lam_g, int64_t ld_lam_g, const double* lam_x, int64_t ld_lam_x,
+                                 const double* g, int64_t ld_g,
+                                 const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx,
+                                 const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg,
+                                 const double* dp, int64_t ld_dp,
+                                 double* dx_out, double* dlam_g_out, double* dX_out, int32_t* info_out,
+                                 double* delta_out, void* stream);
+
+/* Same with HOST pointers; synchronous (staged through the handle's device buffer). */
+int nmpc_solve_tangent_batch(nmpc_handle* h, int32_t B, int32_t nd,
+                             const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                             const double* lam_g, int64_t ld_lam_g, const double* lam_x, int64_t ld_lam_x,
+                             const double* g, int64_t ld_g,
+                             const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx,
+                             const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg,
+                             const double* dp, int64_t ld_dp,
+                             double* dx_out, double* dlam_g_out, double* dX_out, int32_t* info_out,
+                             double* delta_out);
+
 /* Optional per-iteration trace (debugging / parity): when enabled, the next
  * solve records NMPC_TRACE_FIELDS doubles per iteration per scenario into a
  * device buffer readable with nmpc_read_trace (host pointer,

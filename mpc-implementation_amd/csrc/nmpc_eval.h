@@ -154,7 +154,40 @@ constexpr int kSadjSg = kKktWs;
 constexpr int kSadjY = kSadjSg + (5 + NMPC_MAX_OBS) * kEvalStages;
 constexpr int kSadjWs = kSadjY + (5 + NMPC_MAX_OBS) * kEvalStages;
 
+// DEVICE pointers, layouts and leading dimensions as nmpc_solve_tangent_batch_dev
+// (include/nmpc_amd.h); x, p, lam_g, lam_x, the four bounds and dp are required, and one of
+// dx / dlam_g / dX
+struct StanIO {
+  const double *x, *p, *lam_g, *lam_x, *g, *lbx, *ubx, *lbg, *ubg, *dp;
+  long long ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp;
+  int nd;
+  double *dx, *dlam_g, *dX;
+  int* info;
+  double* delta;
+  double* ws;  // B x kStanWs doubles of the handle's workspace
+};
+
+// Per-scenario workspace of the fused forward-mode sensitivity kernel (nmpc_solve_tangent.hip):
+// the fused reverse-mode kernel's, slice for slice -- the KKT kernel's slices, the row weights
+// sigma_s and one direction's jp = (dg/dp) dp where that kernel keeps a seed's y.  Once the
+// factorisation stands the stage summaries' slice holds the unit-weight stage-cost gradients
+// that serve a cost weight taken from p (6 + 6 per stage) and one direction's state tangent
+// (dX/dp) dp (8 per stage).  The per-obstacle curvature lam_{k,o} Hg_o of the
+// parameter-products kernel is recomputed from X and the centres where a centre comes from p,
+// so the union stays within every solver class's workspace (static_assert in
+// nmpc_solve_tangent.hip).
+constexpr int kStanSg = kSadjSg;
+constexpr int kStanJp = kSadjY;
+constexpr int kStanUw = kKktQs;
+constexpr int kStanXi = kStanUw + 12 * kEvalStages;
+constexpr int kStanWs = kSadjWs;
+
 }  // namespace nmpc_impl
+
+// Enqueues the fused forward-mode solution sensitivities of B scenarios on `stream` (one
+// wavefront per scenario, every direction on it: the factorisation is done once).  Same
+// contract as nmpc_eval_launch.
+int nmpc_solve_tangent_launch(const nmpc_impl::Params* dprm, int B, const nmpc_impl::StanIO& io, void* stream);
 
 // Enqueues the fused reverse-mode solution sensitivities of B scenarios on `stream` (one
 // wavefront per scenario, every seed on it: the factorisation is done once).  Same contract as

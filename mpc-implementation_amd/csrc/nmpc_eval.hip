@@ -216,3 +216,6 @@ int nmpc_eval_launch(const Params* dprm, int B, const EvalIO& io, void* stream) 
 
 // the reverse-mode sensitivity of a solution in one launch: a sixth kernel of this unit
 #include "nmpc_solve_adjoint.hip"
+
+// the forward-mode sensitivity of a solution in one launch: a seventh kernel of this unit
+#include "nmpc_solve_tangent.hip"

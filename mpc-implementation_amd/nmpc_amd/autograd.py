@@ -6,8 +6,10 @@
 Forward is :meth:`Solver.solve_device`; backward is :meth:`Solver.sensitivity_adjoint` (one KKT
 solve with one right-hand side and one transposed product per scenario, whatever np is), or with
 ``backward="device"`` one :meth:`Solver.sensitivity_adjoint_device` launch that reads nothing
-back.  This module holds no mathematics of its own.  torch is imported lazily, as the device
-methods do.
+back.  Forward mode (``torch.autograd.forward_ad`` dual tensors on p) gives the tangents of x and
+X: one :meth:`Solver.sensitivity_device` launch with ``backward="device"``,
+:meth:`Solver.sensitivity_fused` otherwise.  This module holds no mathematics of its own.  torch
+is imported lazily, as the device methods do.
 """
 from __future__ import annotations
 
@@ -72,6 +74,31 @@ def _function():
             ref = x_bar if x_bar is not None else X_bar
             return (torch.tensor(g, dtype=torch.float64, device=ref.device),) + (None,) * 7
 
+        @staticmethod
+        def jvp(ctx, p_t, *_):
+            if p_t is None:
+                return None, None
+            B, s = ctx.p.shape[0] if ctx.device else ctx.p.shape[1], ctx.solver
+            f64 = dict(dtype=torch.float64, device=p_t.device)
+            if ctx.device:
+                dp = p_t.detach().to(torch.float64).contiguous().reshape(B, 1, s.np)
+                o = {"dx": torch.empty(B, 1, s.nw, **f64), "dX": torch.empty(B, 1, s.nX, **f64),
+                     "info": torch.empty(B, dtype=torch.int32, device=p_t.device)}
+                s.sensitivity_device(ctx.sol, *ctx.dev, ctx.p, dp, o)
+                ok = (o["info"] == 0) & ((ctx.status == 0) | (ctx.status == 1))
+                nan = float("nan")
+                return tuple(torch.where(ok[:, None], o[k][:, 0, :], torch.full_like(o[k][:, 0, :], nan))
+                             for k in ("dx", "dX"))
+            dp = np.ascontiguousarray(p_t.detach().cpu().numpy().T[:, None, :])  # (np, 1, B)
+            r = ctx.solver.sensitivity_fused(ctx.sol, *ctx.bounds, ctx.p, dp)
+            bad = ~np.isin(ctx.status, _SUCCESS) | (r["info"] != 0)
+            res = []
+            for k in ("dx", "dX"):
+                t = np.ascontiguousarray(r[k][:, 0, :].T)  # (B, n)
+                t[bad] = np.nan
+                res.append(torch.tensor(t, **f64))
+            return tuple(res)
+
     return _Solve
 
 
@@ -88,7 +115,12 @@ def solve(solver, p, lbx, ubx, lbg, ubg, x0=None, backward="host"):
     backward as one :meth:`Solver.sensitivity_adjoint_device` launch: neither pass copies to the
     host or synchronises, so the layer can be enqueued behind other work.  The NaN rows are then
     applied on the device, and an equality row gives a NaN row (``info`` -11) instead of raising.
-    The default ``"host"`` is the three-launch route of :meth:`Solver.sensitivity_adjoint`."""
+    The default ``"host"`` is the three-launch route of :meth:`Solver.sensitivity_adjoint`.
+
+    With a ``torch.autograd.forward_ad`` dual tensor for ``p`` the returned x and X carry the
+    tangents dx* and dX* for p's tangent (one direction per scenario): with ``backward="device"``
+    one :meth:`Solver.sensitivity_device` launch and a ``torch.where`` for the NaN rows, otherwise
+    :meth:`Solver.sensitivity_fused`."""
     if backward not in ("host", "device"):
         raise ValueError(f"backward: expected 'host' or 'device', got {backward!r}")
     return _function().apply(p, solver, lbx, ubx, lbg, ubg, x0, backward == "device")

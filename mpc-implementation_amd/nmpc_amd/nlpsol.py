@@ -1073,6 +1073,145 @@ class Solver:
         _lib.check(_lib.lib().nmpc_solve_adjoint_batch_dev(self._h, B, na, *ins, *outs,
                                                            C.c_void_p(stream.cuda_stream)))
 
+    # ---- forward mode in one launch (nmpc_solve_tangent_batch: weights, ladder, parameter
+    # products, solves)
+    def sensitivity_fused(self, sol: dict, lbx, ubx, lbg, ubg, p, dp):
+        """:meth:`sensitivity` with ``tangent="exact"`` as one kernel launch: the same arguments
+        (``dp`` (np,), (np,nd) or (np,nd,B)), the same dict (``dx`` (nw,nd,B), ``dlam_g``
+        (ng,nd,B), ``info`` (B,), ``delta`` (B,)) and with it ``dX`` (nX,nd,B), the first-order
+        change of the state trajectory X*.  The barrier weights (``sol["g"]`` serves the rows
+        when present, the kernel's own g(x, p) otherwise), the parameter derivatives, the delta
+        ladder and the solves all run on the device; the host only stages the arrays.  A scenario
+        whose ``info`` is not 0 has NaN in dx, dlam_g and dX.  Equality rows raise
+        ``ValueError``, as :meth:`barrier_weights` does."""
+        d = np.asarray(dp, dtype=np.float64)
+        if d.ndim == 1:
+            d = d.reshape(-1, 1)
+        if d.ndim not in (2, 3) or d.shape[0] != self.np or d.shape[1] < 1:
+            raise ValueError(f"dp: expected ({self.np},), ({self.np},nd) or ({self.np},nd,B), got shape {d.shape}")
+        nd = d.shape[1]
+        x, ld_x = self._arg(sol["x"], self.nw, 0.0, "x")
+        B = x.shape[0]
+        ins = [(x, ld_x)]
+        for name, a, n in (("p", p, self.np), ("lam_g", sol["lam_g"], self.ng), ("lam_x", sol["lam_x"], self.nw),
+                           ("g", sol.get("g"), self.ng), ("lbx", lbx, self.nw), ("ubx", ubx, self.nw),
+                           ("lbg", lbg, self.ng), ("ubg", ubg, self.ng)):
+            if a is None:
+                ins.append((None, 0))
+                continue
+            a, ld = self._arg(a, n, 0.0, name)
+            if ld and a.shape[0] != B:
+                raise ValueError(f"{name}: batch size {a.shape[0]} does not match {B}")
+            ins.append((a, ld))
+        if d.ndim == 3:
+            if d.shape[2] != B:
+                raise ValueError(f"dp: batch size {d.shape[2]} does not match {B}")
+            ins.append((np.ascontiguousarray(d.transpose(2, 1, 0)), self.np * nd))  # (B, nd, np)
+        else:
+            ins.append((np.ascontiguousarray(d.T), 0))  # (nd, np), shared
+        out = {"dx": np.empty((B, nd, self.nw)), "dlam_g": np.empty((B, nd, self.ng)), "dX": np.empty((B, nd, self.nX))}
+        info, delta = np.empty(B, dtype=np.int32), np.empty(B)
+        flat = []
+        for a, ld in ins:
+            flat += [_dptr(a) if a is not None else None, ld]
+        _lib.check(_lib.lib().nmpc_solve_tangent_batch(
+            self._h, B, nd, *flat, _dptr(out["dx"]), _dptr(out["dlam_g"]), _dptr(out["dX"]),
+            info.ctypes.data_as(_IP), _dptr(delta)))
+        if np.any(info == -11):
+            lo, hi = (np.asarray(v, dtype=np.float64).reshape(self.ng, -1) for v in (lbg, ubg))
+            if np.any(lo == hi):
+                raise ValueError("sensitivity_fused: equality rows (lbg == ubg) are not supported")
+        res = {k: np.ascontiguousarray(t.transpose(2, 1, 0)) for k, t in out.items()}
+        res["info"], res["delta"] = info, delta
+        return res
+
+    def sensitivity_device(self, sol: dict, lbx, ubx, lbg, ubg, p, dp, out: dict, stream=None):
+        """Device path of :meth:`sensitivity_fused`: torch CUDA float64 tensors.  ``sol`` holds x
+        (B,nw), lam_g (B,ng), lam_x (B,nw) and optionally g (B,ng) as :meth:`solve_device` leaves
+        them; the bounds and ``p`` are scenario-major (B, n) or shared (n,); ``dp`` is (B, nd, np)
+        or shared (nd, np); ``out`` holds preallocated device tensors, any of dx (B,nd,nw), dlam_g
+        (B,nd,ng), dX (B,nd,nX), info (B,) int32 and delta (B,) -- dx, dlam_g or dX at least.  A
+        scenario whose ``info`` is not 0 (1: no rung of the delta ladder factorises; -11: an
+        equality row, lbx > ubx or a NaN multiplier) has NaN in dx, dlam_g and dX.  Enqueued on
+        ``stream`` (default = current); never synchronises the host and reads nothing back."""
+        import torch  # plumbing only: device memory and streams
+
+        given = [out[k] for k in ("dx", "dlam_g", "dX") if out.get(k) is not None]
+        if not given:
+            raise ValueError("sensitivity_device: out holds none of dx, dlam_g, dX")
+        if dp is None:
+            raise ValueError("dp is required")
+        B, nd = given[0].shape[0], given[0].shape[1]
+
+        def dv(t, n, name):
+            if t is None:
+                return C.c_void_p(0), 0
+            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), name
+            if t.dim() == 1:
+                assert t.shape[0] == n, name
+                return C.c_void_p(t.data_ptr()), 0
+            assert t.shape == (B, n), (name, tuple(t.shape), (B, n))
+            return C.c_void_p(t.data_ptr()), n
+
+        for k in ("x", "lam_g", "lam_x"):
+            if sol.get(k) is None:
+                raise ValueError(f"sol: {k} is required")
+        ins = []
+        for name, t, n in (("x", sol["x"], self.nw), ("p", p, self.np), ("lam_g", sol["lam_g"], self.ng),
+                           ("lam_x", sol["lam_x"], self.nw), ("g", sol.get("g"), self.ng), ("lbx", lbx, self.nw),
+                           ("ubx", ubx, self.nw), ("lbg", lbg, self.ng), ("ubg", ubg, self.ng)):
+            if t is None and name != "g":
+                raise ValueError(f"{name} is required")
+            ins += list(dv(t, n, name))
+        assert dp.dtype == torch.float64 and dp.is_cuda and dp.is_contiguous(), "dp"
+        assert tuple(dp.shape) in ((nd, self.np), (B, nd, self.np)), ("dp", tuple(dp.shape))
+        ins += [C.c_void_p(dp.data_ptr()), 0 if dp.dim() == 2 else nd * self.np]
+        outs = []
+        for k, n in (("dx", self.nw), ("dlam_g", self.ng), ("dX", self.nX)):
+            t = out.get(k)
+            if t is not None:
+                assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B, nd, n), k
+            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
+        for k, dt in (("info", torch.int32), ("delta", torch.float64)):
+            t = out.get(k)
+            if t is not None:
+                assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B,), k
+            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        _lib.check(_lib.lib().nmpc_solve_tangent_batch_dev(self._h, B, nd, *ins, *outs,
+                                                           C.c_void_p(stream.cuda_stream)))
+
+    def feedback_gain_device(self, sol: dict, lbx, ubx, lbg, ubg, p, out: dict | None = None, stream=None):
+        """Returns ``(K, info)``: the NMPC law's feedback gain K = d u0* / d x0, (B, nu, nx), and
+        ``info`` (B,) int32, as CUDA tensors: :meth:`sensitivity_device` for the nx unit directions of p's x0 block,
+        shared by every scenario, and the first nu entries of each dx arranged by torch on the
+        same stream.  ``sol``, the bounds and ``p`` as :meth:`sensitivity_device` takes them;
+        ``out`` may hold a preallocated ``K`` and ``info``.  Between two solves u0* + K (x0' - x0)
+        is the law's first-order answer to a measured state x0'.  A scenario whose ``info`` is
+        not 0 has NaN in K.  Nothing is copied to the host and nothing synchronises."""
+        import torch
+
+        x = sol["x"]
+        B, nu, nx = x.shape[0], self.nw // self.spec.N, self.nX // (self.spec.N + 1)
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        with torch.cuda.stream(stream):
+            dp = torch.zeros(nx, self.np, dtype=torch.float64, device=x.device)
+            dp[:, :nx] = torch.eye(nx, dtype=torch.float64, device=x.device)
+            o = {"dx": torch.empty(B, nx, self.nw, dtype=torch.float64, device=x.device),
+                 "info": (out or {}).get("info")}
+            if o["info"] is None:
+                o["info"] = torch.empty(B, dtype=torch.int32, device=x.device)
+            self.sensitivity_device(sol, lbx, ubx, lbg, ubg, p, dp, o, stream=stream)
+            K = o["dx"][:, :, :nu].transpose(1, 2)  # (B, nu, nx): column j is d u0 / d x0_j
+            if (out or {}).get("K") is not None:
+                out["K"].copy_(K)
+                K = out["K"]
+            else:
+                K = K.contiguous()
+        return K, o["info"]
+
     def shift_device(self, p, u_sol, w_out, v_t, w_t, stream=None):
         """Closed-loop shift on device (Python/NMPC_TT.py:13-30), see nmpc_shift_dev."""
         import torch
