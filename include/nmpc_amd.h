@@ -538,6 +538,59 @@ int nmpc_solve_tangent_batch(nmpc_handle* h, int32_t B, int32_t nd,
                              double* dx_out, double* dlam_g_out, double* dX_out, int32_t* info_out,
                              double* delta_out);
 
+/* The feedback policy along a SOLUTION's plan, for a whole batch, in one launch: what a controller
+ * needs to act between two solves,
+ *   u_k(x, p') ~ u*_k + K_k (x - X*_k) + sum_d kff_k^(d) c_d,      p' - p = sum_d c_d dp_d.
+ * The point (x, lam_g, lam_x, p, g and the four bounds), the barrier weights, the fixed-variable
+ * rule, the validity rules (info = -11), the condensed matrix M and its delta ladder (info = 1),
+ * leading dimensions, ld = 0 sharing and the +-1e19 rule are those of nmpc_solve_tangent_batch_dev
+ * (above).  With obj_factor = 1 and the stage terms of M's Riccati recursion at the ladder's delta,
+ *   R~_k = R_k + B'P_{k+1}B,  S~_k = S_k + B'P_{k+1}A,  K_k = -R~_k^-1 S~_k,  k = N-1 ... 0,
+ * where, unlike in every other entry point, stage 0's cross term S_0 = d2_xu (lam_1' T f)' is part
+ * of the recursion (Q_0 stays 0): it changes no solve, since K_0 multiplies a zero state step
+ * there, and makes K_0 the stage-0 gain.  For each of nd >= 0 directions dp_d, with the
+ * right-hand side and xi = (dX/dp) dp_d of nmpc_solve_tangent_batch_dev and the recursion's k_k,
+ *   kff_k = k_k - K_k xi_k,
+ * so that dx_k = K_k dX_k + kff_k for that entry point's dx and dX, every k = 0 ... N-1.
+ * Outputs, per scenario, in the model's own dimensions (the no-gimbal model: nu = 3, nx = 5):
+ *   K_out   (nu nx N x B)  : block k is K_k, nu x nx column-major: (i, j) at k nu nx + j nu + i
+ *   kff_out (nw nd x B)    : direction d occupies [d nw, (d+1) nw), in dx_out's layout
+ *   A_out   (nx nx N x B)  : block k is A_k = d x_{k+1} / d x_k of x_{k+1} = x_k + T f(x_k, u_k)
+ *                            at (X*, x*), column-major
+ *   B_out   (nx nu N x B)  : block k is B_k = d x_{k+1} / d u_k, nx x nu column-major
+ *   X_out   (nx(N+1) x B)  : X*, the kernel's own rollout
+ *   info_out, delta_out (B): as nmpc_solve_tangent_batch_dev's
+ * Each may be NULL; at least one of K_out, kff_out, A_out, B_out must be given.  With info != 0
+ * every output of the scenario is NaN and its neighbours are untouched.  A variable with
+ * lbx == ubx is fixed: its row of every K_k and its entry of kff are exactly 0.  nd = 0 is allowed;
+ * dp and kff_out must then be NULL.  Directions are independent of each other.
+ * DEVICE pointers, enqueued on `stream`; never synchronises, and allocates nothing once the
+ * handle's workspace covers B (a solve's workspace does).
+ * A NULL handle, B <= 0, nd < 0, a NULL x, p, lam_g, lam_x, lbx, ubx, lbg or ubg, a NULL dp with
+ * nd > 0, a dp or kff_out with nd = 0, K_out, kff_out, A_out and B_out all NULL, or a leading
+ * dimension that is neither 0 nor >= the vector length (np nd for dp) return NMPC_E_INVALID before
+ * any device call. */
+int nmpc_solve_policy_batch_dev(nmpc_handle* h, int32_t B, int32_t nd,
+                                const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                                const double* lam_g, int64_t ld_lam_g, const double* lam_x, int64_t ld_lam_x,
+                                const double* g, int64_t ld_g,
+                                const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx,
+                                const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg,
+                                const double* dp, int64_t ld_dp,
+                                double* K_out, double* kff_out, double* A_out, double* B_out, double* X_out,
+                                int32_t* info_out, double* delta_out, void* stream);
+
+/* Same with HOST pointers; synchronous (staged through the handle's device buffer). */
+int nmpc_solve_policy_batch(nmpc_handle* h, int32_t B, int32_t nd,
+                            const double* x, int64_t ld_x, const double* p, int64_t ld_p,
+                            const double* lam_g, int64_t ld_lam_g, const double* lam_x, int64_t ld_lam_x,
+                            const double* g, int64_t ld_g,
+                            const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx,
+                            const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg,
+                            const double* dp, int64_t ld_dp,
+                            double* K_out, double* kff_out, double* A_out, double* B_out, double* X_out,
+                            int32_t* info_out, double* delta_out);
+
 /* Optional per-iteration trace (debugging / parity): when enabled, the next
  * solve records NMPC_TRACE_FIELDS doubles per iteration per scenario into a
  * device buffer readable with nmpc_read_trace (host pointer,

@@ -182,7 +182,28 @@ constexpr int kStanUw = kKktQs;
 constexpr int kStanXi = kStanUw + 12 * kEvalStages;
 constexpr int kStanWs = kSadjWs;
 
+// DEVICE pointers, layouts and leading dimensions as nmpc_solve_policy_batch_dev
+// (include/nmpc_amd.h); x, p, lam_g, lam_x and the four bounds are required, dp where nd > 0,
+// and one of K / kff / A / Bm
+struct SpolIO {
+  const double *x, *p, *lam_g, *lam_x, *g, *lbx, *ubx, *lbg, *ubg, *dp;
+  long long ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp;
+  int nd;
+  double *K, *kff, *A, *Bm, *X;
+  int* info;
+  double* delta;
+  double* ws;  // B x kSpolWs doubles of the handle's workspace
+};
+
+// Per-scenario workspace of the feedback-policy kernel (nmpc_solve_policy.hip): the fused
+// forward-mode kernel's, slice for slice and used the same way.
+constexpr int kSpolWs = kStanWs;
+
 }  // namespace nmpc_impl
+
+// Enqueues the feedback policies of B scenarios on `stream` (one wavefront per scenario, every
+// direction on it: the factorisation is done once).  Same contract as nmpc_eval_launch.
+int nmpc_solve_policy_launch(const nmpc_impl::Params* dprm, int B, const nmpc_impl::SpolIO& io, void* stream);
 
 // Enqueues the fused forward-mode solution sensitivities of B scenarios on `stream` (one
 // wavefront per scenario, every direction on it: the factorisation is done once).  Same

@@ -219,3 +219,6 @@ int nmpc_eval_launch(const Params* dprm, int B, const EvalIO& io, void* stream) 
 
 // the forward-mode sensitivity of a solution in one launch: a seventh kernel of this unit
 #include "nmpc_solve_tangent.hip"
+
+// the plan's feedback policy (stage gains and feedforward) in one launch: an eighth kernel of this unit
+#include "nmpc_solve_policy.hip"

@@ -6384,6 +6384,121 @@ int nmpc_solve_tangent_batch(nmpc_handle* h, int32_t B, int32_t nd, const double
   return NMPC_OK;
 }
 
+// ---- the plan's feedback policy in one launch (kernel: nmpc_solve_policy.hip)
+struct SpolArgs {
+  // x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp
+  const double* in[10];
+  int64_t ld[10];
+  // K, kff, A, B, X, delta
+  double* out[6];
+  int32_t* info;
+};
+// per-scenario lengths of the six double outputs
+static void spol_out_lengths(const Params& P, int32_t nd, size_t olen[6]) {
+  const size_t nu = P.nuE, nx = P.nxE, N = P.N;
+  const size_t v[6] = {nu * nx * N, (size_t)P.nwE * (size_t)nd, nx * nx * N, nx * nu * N, nx * (N + 1), 1};
+  for (int i = 0; i < 6; ++i) olen[i] = v[i];
+}
+// the argument checks of both entry points: nothing here touches the device
+static int spol_check(const nmpc_handle* h, int32_t B, int32_t nd, const SpolArgs& a) {
+  if (!h) return fail(NMPC_E_INVALID, "null handle");
+  if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
+  if (nd < 0) return fail(NMPC_E_INVALID, "nd < 0");
+  for (int i = 0; i < 9; ++i)
+    if (i != 4 && !a.in[i])
+      return fail(NMPC_E_INVALID, "required pointer is null (x, p, lam_g, lam_x, lbx, ubx, lbg, ubg)");
+  if (nd > 0 && !a.in[9]) return fail(NMPC_E_INVALID, "dp is null with nd > 0");
+  if (nd == 0 && (a.in[9] || a.out[1])) return fail(NMPC_E_INVALID, "dp and kff_out must be null with nd = 0");
+  if (!a.out[0] && !a.out[1] && !a.out[2] && !a.out[3])
+    return fail(NMPC_E_INVALID, "K_out, kff_out, A_out and B_out are all null");
+  size_t vlen[10];
+  stan_lengths(h->hp, nd, vlen);
+  for (int i = 0; i < 10; ++i)
+    if (a.in[i] && a.ld[i] != 0 && a.ld[i] < (int64_t)vlen[i])
+      return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
+  return NMPC_OK;
+}
+// checked arguments, DEVICE pointers: workspace from the handle (sized like a solve's, grown
+// only when it does not cover B yet), then one launch
+static int spol_enqueue(nmpc_handle* h, int32_t B, int32_t nd, const SpolArgs& a, void* stream) {
+  const int per = h->ws_doubles > kSpolWs ? h->ws_doubles : kSpolWs;
+  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
+  SpolIO io;
+  io.x = a.in[0]; io.p = a.in[1]; io.lam_g = a.in[2]; io.lam_x = a.in[3]; io.g = a.in[4];
+  io.lbx = a.in[5]; io.ubx = a.in[6]; io.lbg = a.in[7]; io.ubg = a.in[8]; io.dp = a.in[9];
+  io.ld_x = a.ld[0]; io.ld_p = a.ld[1]; io.ld_lam_g = a.ld[2]; io.ld_lam_x = a.ld[3]; io.ld_g = a.ld[4];
+  io.ld_lbx = a.ld[5]; io.ld_ubx = a.ld[6]; io.ld_lbg = a.ld[7]; io.ld_ubg = a.ld[8]; io.ld_dp = a.ld[9];
+  io.nd = nd;
+  io.K = a.out[0]; io.kff = a.out[1]; io.A = a.out[2]; io.Bm = a.out[3]; io.X = a.out[4]; io.delta = a.out[5];
+  io.info = a.info;
+  io.ws = h->dws;
+  const hipError_t e = (hipError_t)nmpc_solve_policy_launch(h->dprm, (int)B, io, stream);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("solve policy launch: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
+int nmpc_solve_policy_batch_dev(nmpc_handle* h, int32_t B, int32_t nd, const double* x, int64_t ld_x,
+                                const double* p, int64_t ld_p, const double* lam_g, int64_t ld_lam_g,
+                                const double* lam_x, int64_t ld_lam_x, const double* g, int64_t ld_g,
+                                const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx,
+                                const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg,
+                                const double* dp, int64_t ld_dp, double* K_out, double* kff_out, double* A_out,
+                                double* B_out, double* X_out, int32_t* info_out, double* delta_out, void* stream) {
+  const SpolArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
+                   {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp},
+                   {K_out, kff_out, A_out, B_out, X_out, delta_out}, info_out};
+  if (int rc = spol_check(h, B, nd, a)) return rc;
+  return spol_enqueue(h, B, nd, a, stream);
+}
+
+int nmpc_solve_policy_batch(nmpc_handle* h, int32_t B, int32_t nd, const double* x, int64_t ld_x, const double* p,
+                            int64_t ld_p, const double* lam_g, int64_t ld_lam_g, const double* lam_x,
+                            int64_t ld_lam_x, const double* g, int64_t ld_g, const double* lbx, int64_t ld_lbx,
+                            const double* ubx, int64_t ld_ubx, const double* lbg, int64_t ld_lbg,
+                            const double* ubg, int64_t ld_ubg, const double* dp, int64_t ld_dp, double* K_out,
+                            double* kff_out, double* A_out, double* B_out, double* X_out, int32_t* info_out,
+                            double* delta_out) {
+  const SpolArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
+                   {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp},
+                   {K_out, kff_out, A_out, B_out, X_out, delta_out}, info_out};
+  if (int rc = spol_check(h, B, nd, a)) return rc;
+  const Params& P = h->hp;
+  // staging: the ten inputs (absent ones take no room), the six outputs, the verdicts
+  size_t vlen[10], n_in[10], olen[6], total = 0;
+  stan_lengths(P, nd, vlen);
+  spol_out_lengths(P, nd, olen);
+  for (int i = 0; i < 10; ++i) {
+    n_in[i] = !a.in[i] ? 0 : (a.ld[i] == 0 ? vlen[i] : (size_t)(B - 1) * (size_t)a.ld[i] + vlen[i]);
+    total += n_in[i];
+  }
+  for (int i = 0; i < 6; ++i) total += a.out[i] ? (size_t)B * olen[i] : 0;
+  total += info_out ? ((size_t)B + 1) / 2 : 0;  // B int32 in whole doubles
+  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
+  double* q = h->dbuf;
+  SpolArgs d = a;
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 10; ++i) {
+    d.in[i] = a.in[i] ? q : nullptr;
+    if (a.in[i] && e == hipSuccess) e = hipMemcpy(q, a.in[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
+    q += n_in[i];
+  }
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
+  for (int i = 0; i < 6; ++i) {
+    d.out[i] = a.out[i] ? q : nullptr;
+    q += a.out[i] ? (size_t)B * olen[i] : 0;
+  }
+  d.info = info_out ? (int32_t*)q : nullptr;
+  if (int rc = spol_enqueue(h, B, nd, d, nullptr)) return rc;
+  e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
+  for (int i = 0; i < 6; ++i)
+    if (a.out[i] && e == hipSuccess)
+      e = hipMemcpy(a.out[i], d.out[i], (size_t)B * olen[i] * sizeof(double), hipMemcpyDeviceToHost);
+  if (info_out && e == hipSuccess) e = hipMemcpy(info_out, d.info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
 int nmpc_shift_dev(nmpc_handle* h, int32_t B, double* p, int64_t ld_p, const double* u_sol, double* w_out,
                    const double* v_t, const double* w_t, void* stream) {
   if (!h) return fail(NMPC_E_INVALID, "null handle");

@@ -1212,6 +1212,138 @@ class Solver:
                 K = K.contiguous()
         return K, o["info"]
 
+    def _policy_dims(self):
+        N = self.spec.N
+        return N, self.nw // N, self.nX // (N + 1)
+
+    def policy_fused(self, sol: dict, lbx, ubx, lbg, ubg, p, dp=None):
+        """The feedback policy along the plan through the host entry point
+        (``nmpc_solve_policy_batch``): the arguments of :meth:`sensitivity_fused` (``dp`` (np,),
+        (np,nd), (np,nd,B) or None for no direction).  Returns NumPy arrays in the C layout's
+        order: ``K`` (B,N,nu,nx), ``kff`` (B,nd,N,nu) (None without directions), ``A``
+        (B,N,nx,nx), ``B`` (B,N,nx,nu), ``X`` (B,N+1,nx), ``info`` (B,), ``delta`` (B,).  A
+        scenario whose ``info`` is not 0 has NaN in every array.  Equality rows raise
+        ``ValueError``, as :meth:`sensitivity_fused` does."""
+        N, nu, nx = self._policy_dims()
+        d = None
+        nd = 0
+        if dp is not None:
+            d = np.asarray(dp, dtype=np.float64)
+            if d.ndim == 1:
+                d = d.reshape(-1, 1)
+            if d.ndim not in (2, 3) or d.shape[0] != self.np:
+                raise ValueError(f"dp: expected ({self.np},), ({self.np},nd) or ({self.np},nd,B), got shape {d.shape}")
+            nd = d.shape[1]
+            if nd == 0:
+                d = None
+        x, ld_x = self._arg(sol["x"], self.nw, 0.0, "x")
+        B = x.shape[0]
+        ins = [(x, ld_x)]
+        for name, a, n in (("p", p, self.np), ("lam_g", sol["lam_g"], self.ng), ("lam_x", sol["lam_x"], self.nw),
+                           ("g", sol.get("g"), self.ng), ("lbx", lbx, self.nw), ("ubx", ubx, self.nw),
+                           ("lbg", lbg, self.ng), ("ubg", ubg, self.ng)):
+            if a is None:
+                ins.append((None, 0))
+                continue
+            a, ld = self._arg(a, n, 0.0, name)
+            if ld and a.shape[0] != B:
+                raise ValueError(f"{name}: batch size {a.shape[0]} does not match {B}")
+            ins.append((a, ld))
+        if d is None:
+            ins.append((None, 0))
+        elif d.ndim == 3:
+            if d.shape[2] != B:
+                raise ValueError(f"dp: batch size {d.shape[2]} does not match {B}")
+            ins.append((np.ascontiguousarray(d.transpose(2, 1, 0)), self.np * nd))  # (B, nd, np)
+        else:
+            ins.append((np.ascontiguousarray(d.T), 0))  # (nd, np), shared
+        K, A, Bm = np.empty((B, N, nx, nu)), np.empty((B, N, nx, nx)), np.empty((B, N, nu, nx))
+        kff = np.empty((B, nd, N, nu)) if nd else None
+        X = np.empty((B, N + 1, nx))
+        info, delta = np.empty(B, dtype=np.int32), np.empty(B)
+        flat = []
+        for a, ld in ins:
+            flat += [_dptr(a) if a is not None else None, ld]
+        _lib.check(_lib.lib().nmpc_solve_policy_batch(
+            self._h, B, nd, *flat, _dptr(K), _dptr(kff) if nd else None, _dptr(A), _dptr(Bm), _dptr(X),
+            info.ctypes.data_as(_IP), _dptr(delta)))
+        if np.any(info == -11):
+            lo, hi = (np.asarray(v, dtype=np.float64).reshape(self.ng, -1) for v in (lbg, ubg))
+            if np.any(lo == hi):
+                raise ValueError("policy_fused: equality rows (lbg == ubg) are not supported")
+        # the blocks are column-major: K_k is stored (nx, nu), A_k (nx, nx), B_k (nu, nx)
+        return {"K": np.ascontiguousarray(K.transpose(0, 1, 3, 2)), "kff": kff,
+                "A": np.ascontiguousarray(A.transpose(0, 1, 3, 2)), "B": np.ascontiguousarray(Bm.transpose(0, 1, 3, 2)),
+                "X": X, "info": info, "delta": delta}
+
+    def policy_device(self, sol: dict, lbx, ubx, lbg, ubg, p, dp=None, out: dict | None = None, stream=None):
+        """The feedback policy along the plan (``nmpc_solve_policy_batch_dev``), torch CUDA float64
+        tensors in and out: ``sol``, the bounds, ``p`` and ``dp`` ((B,nd,np), shared (nd,np), or
+        None for no direction) as :meth:`sensitivity_device` takes them.  Returns a dict of
+        ``K`` (B,N,nu,nx), the stage gains; ``kff`` (B,nd,N,nu), the feedforward per direction
+        (None without directions); ``A`` (B,N,nx,nx) and ``B`` (B,N,nx,nu), the stage matrices of
+        x_{k+1} = x_k + T f(x_k, u_k); ``X`` (B,N+1,nx), the plan's states; ``info`` (B,) int32 and
+        ``delta`` (B,).  K, A and B are transposed views of the kernel's column-major blocks.
+        ``out`` may hold the raw buffers of an earlier call (the returned dict's ``"raw"``) to
+        reuse them.  A scenario whose ``info`` is not 0 has NaN everywhere.  Enqueued on
+        ``stream`` (default = current); never synchronises the host and reads nothing back."""
+        import torch  # plumbing only: device memory and streams
+
+        N, nu, nx = self._policy_dims()
+        for k in ("x", "lam_g", "lam_x"):
+            if sol.get(k) is None:
+                raise ValueError(f"sol: {k} is required")
+        x = sol["x"]
+        B = x.shape[0]
+        nd = 0 if dp is None else dp.shape[-2]
+        if nd == 0:
+            dp = None
+
+        def dv(t, n, name):
+            if t is None:
+                return C.c_void_p(0), 0
+            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), name
+            if t.dim() == 1:
+                assert t.shape[0] == n, name
+                return C.c_void_p(t.data_ptr()), 0
+            assert t.shape == (B, n), (name, tuple(t.shape), (B, n))
+            return C.c_void_p(t.data_ptr()), n
+
+        ins = []
+        for name, t, n in (("x", x, self.nw), ("p", p, self.np), ("lam_g", sol["lam_g"], self.ng),
+                           ("lam_x", sol["lam_x"], self.nw), ("g", sol.get("g"), self.ng), ("lbx", lbx, self.nw),
+                           ("ubx", ubx, self.nw), ("lbg", lbg, self.ng), ("ubg", ubg, self.ng)):
+            if t is None and name != "g":
+                raise ValueError(f"{name} is required")
+            ins += list(dv(t, n, name))
+        if dp is not None:
+            assert dp.dtype == torch.float64 and dp.is_cuda and dp.is_contiguous(), "dp"
+            assert tuple(dp.shape) in ((nd, self.np), (B, nd, self.np)), ("dp", tuple(dp.shape))
+            ins += [C.c_void_p(dp.data_ptr()), 0 if dp.dim() == 2 else nd * self.np]
+        else:
+            ins += [C.c_void_p(0), 0]
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        shapes = {"K": (B, N, nx, nu), "kff": (B, nd, N, nu), "A": (B, N, nx, nx), "B": (B, N, nu, nx),
+                  "X": (B, N + 1, nx), "info": (B,), "delta": (B,)}
+        raw = {}
+        with torch.cuda.stream(stream):
+            for k, shp in shapes.items():
+                if k == "kff" and nd == 0:
+                    raw[k] = None
+                    continue
+                dt = torch.int32 if k == "info" else torch.float64
+                t = (out or {}).get(k)
+                if t is not None:
+                    assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp, k
+                else:
+                    t = torch.empty(shp, dtype=dt, device=x.device)
+                raw[k] = t
+        ptr = [C.c_void_p(raw[k].data_ptr()) if raw[k] is not None else C.c_void_p(0) for k in shapes]
+        _lib.check(_lib.lib().nmpc_solve_policy_batch_dev(self._h, B, nd, *ins, *ptr, C.c_void_p(stream.cuda_stream)))
+        return {"K": raw["K"].transpose(2, 3), "kff": raw["kff"], "A": raw["A"].transpose(2, 3),
+                "B": raw["B"].transpose(2, 3), "X": raw["X"], "info": raw["info"], "delta": raw["delta"], "raw": raw}
+
     def shift_device(self, p, u_sol, w_out, v_t, w_t, stream=None):
         """Closed-loop shift on device (Python/NMPC_TT.py:13-30), see nmpc_shift_dev."""
         import torch
