@@ -128,76 +128,60 @@ struct AdjIO {
 // (static_assert in nmpc_adjoint.hip).
 constexpr int kAdjWs = kPprodWs;
 
+// What the three kernels at a solve's point (x*, lam_g*, lam_x*) take alike (nmpc_point.hip):
 // DEVICE pointers, layouts and leading dimensions as nmpc_solve_adjoint_batch_dev
-// (include/nmpc_amd.h); x, p, lam_g, lam_x and the four bounds are required, one of the seeds
-// x_bar / lam_g_bar / X_bar and one of pbar / q
+// (include/nmpc_amd.h).  x, p, lam_g, lam_x and the four bounds are required; g, info and delta
+// may be null
+struct PointIO {
+  const double *x, *p, *lam_g, *lam_x, *g, *lbx, *ubx, *lbg, *ubg;
+  long long ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg;
+  int* info;
+  double* delta;
+  double* ws;  // B x kPointWs doubles of the handle's workspace
+};
+
+// Per-scenario workspace of those kernels: the KKT kernel's slices, used the same way (the
+// gradient slice also holds each seed's stage sources or each direction's h_k, as in the
+// adjoint- and parameter-products kernels), the row weights sigma_s and one seed's row seed
+// y = sigma_s (lam_g_bar - J q) or one direction's jp = (dg/dp) dp.  Once the factorisation
+// stands the stage summaries' slice holds the unit-weight stage-cost gradients that serve a cost
+// weight taken from p (6 + 6 per stage) and one direction's state tangent (dX/dp) dp (8 per
+// stage).  The per-obstacle curvature lam_{k,o} Hg_o of the products kernels is recomputed from
+// X and the centres where a centre comes from p, so the union stays within every solver class's
+// workspace (static_assert in nmpc_point.hip).
+constexpr int kPointSg = kKktWs;
+constexpr int kPointY = kPointSg + (5 + NMPC_MAX_OBS) * kEvalStages;
+constexpr int kPointWs = kPointY + (5 + NMPC_MAX_OBS) * kEvalStages;
+constexpr int kPointUw = kKktQs;
+constexpr int kPointXi = kPointUw + 12 * kEvalStages;
+
+// nmpc_solve_adjoint_batch_dev's own arguments: one of the seeds x_bar / lam_g_bar / X_bar and
+// one of pbar / q are required
 struct SadjIO {
-  const double *x, *p, *lam_g, *lam_x, *g, *lbx, *ubx, *lbg, *ubg, *x_bar, *lam_g_bar, *X_bar;
-  long long ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_x_bar, ld_lam_g_bar, ld_X_bar;
+  PointIO pt;
+  const double *x_bar, *lam_g_bar, *X_bar;
+  long long ld_x_bar, ld_lam_g_bar, ld_X_bar;
   int na;
   double *pbar, *q, *jq;
-  int* info;
-  double* delta;
-  double* ws;  // B x kSadjWs doubles of the handle's workspace
 };
 
-// Per-scenario workspace of the fused reverse-mode sensitivity kernel (nmpc_solve_adjoint.hip):
-// the KKT kernel's slices, used the same way (the gradient slice also holds each seed's stage
-// sources, as in the adjoint-products kernel), the row weights sigma_s and one seed's row seed
-// y = sigma_s (lam_g_bar - J q).  The unit-weight stage-cost gradients that serve a cost weight
-// taken from p (6 + 6 per stage) take the stage summaries' slice once the factorisation stands.
-// The per-obstacle curvature lam_{k,o} Hg_o of the
-// adjoint-products kernel is recomputed from X and the centres where a centre comes from p, so
-// the union stays within every solver class's workspace (static_assert in
-// nmpc_solve_adjoint.hip).
-constexpr int kSadjSg = kKktWs;
-constexpr int kSadjY = kSadjSg + (5 + NMPC_MAX_OBS) * kEvalStages;
-constexpr int kSadjWs = kSadjY + (5 + NMPC_MAX_OBS) * kEvalStages;
-
-// DEVICE pointers, layouts and leading dimensions as nmpc_solve_tangent_batch_dev
-// (include/nmpc_amd.h); x, p, lam_g, lam_x, the four bounds and dp are required, and one of
-// dx / dlam_g / dX
+// nmpc_solve_tangent_batch_dev's own arguments: dp is required, and one of dx / dlam_g / dX
 struct StanIO {
-  const double *x, *p, *lam_g, *lam_x, *g, *lbx, *ubx, *lbg, *ubg, *dp;
-  long long ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp;
+  PointIO pt;
+  const double* dp;
+  long long ld_dp;
   int nd;
   double *dx, *dlam_g, *dX;
-  int* info;
-  double* delta;
-  double* ws;  // B x kStanWs doubles of the handle's workspace
 };
 
-// Per-scenario workspace of the fused forward-mode sensitivity kernel (nmpc_solve_tangent.hip):
-// the fused reverse-mode kernel's, slice for slice -- the KKT kernel's slices, the row weights
-// sigma_s and one direction's jp = (dg/dp) dp where that kernel keeps a seed's y.  Once the
-// factorisation stands the stage summaries' slice holds the unit-weight stage-cost gradients
-// that serve a cost weight taken from p (6 + 6 per stage) and one direction's state tangent
-// (dX/dp) dp (8 per stage).  The per-obstacle curvature lam_{k,o} Hg_o of the
-// parameter-products kernel is recomputed from X and the centres where a centre comes from p,
-// so the union stays within every solver class's workspace (static_assert in
-// nmpc_solve_tangent.hip).
-constexpr int kStanSg = kSadjSg;
-constexpr int kStanJp = kSadjY;
-constexpr int kStanUw = kKktQs;
-constexpr int kStanXi = kStanUw + 12 * kEvalStages;
-constexpr int kStanWs = kSadjWs;
-
-// DEVICE pointers, layouts and leading dimensions as nmpc_solve_policy_batch_dev
-// (include/nmpc_amd.h); x, p, lam_g, lam_x and the four bounds are required, dp where nd > 0,
-// and one of K / kff / A / Bm
+// nmpc_solve_policy_batch_dev's own arguments: dp where nd > 0, and one of K / kff / A / Bm
 struct SpolIO {
-  const double *x, *p, *lam_g, *lam_x, *g, *lbx, *ubx, *lbg, *ubg, *dp;
-  long long ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp;
+  PointIO pt;
+  const double* dp;
+  long long ld_dp;
   int nd;
   double *K, *kff, *A, *Bm, *X;
-  int* info;
-  double* delta;
-  double* ws;  // B x kSpolWs doubles of the handle's workspace
 };
-
-// Per-scenario workspace of the feedback-policy kernel (nmpc_solve_policy.hip): the fused
-// forward-mode kernel's, slice for slice and used the same way.
-constexpr int kSpolWs = kStanWs;
 
 }  // namespace nmpc_impl
 

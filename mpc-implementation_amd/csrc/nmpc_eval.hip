@@ -214,6 +214,9 @@ int nmpc_eval_launch(const Params* dprm, int B, const EvalIO& io, void* stream) 
 // the adjoint (transposed) products at given points: a fifth kernel of this unit
 #include "nmpc_adjoint.hip"
 
+// what the kernels at a solve's point share (no kernel of its own)
+#include "nmpc_point.hip"
+
 // the reverse-mode sensitivity of a solution in one launch: a sixth kernel of this unit
 #include "nmpc_solve_adjoint.hip"
 

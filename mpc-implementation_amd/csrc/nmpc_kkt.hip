@@ -62,6 +62,13 @@ constexpr int K_TOTAL = K_FIX + NS / 2 + 2;
 static_assert(8 * NS >= 144, "the sweeps' P / p buffers live in the prefix-sum scratch");
 static_assert(K_TOTAL * 8 <= 32 * 1024, "KKT kernel LDS");
 
+// nmpc_point.hip's (later in this unit): the scenario load and the stage summary that this kernel
+// shares with the kernels at a solve's point
+__device__ __forceinline__ void point_load(Solver<CapEv>& S, const Params* __restrict__ prm, int lane,
+                                           const double* pb, const double* xb);
+__device__ __forceinline__ void point_summary(Solver<CapEv>& S, int k, double obj_factor, const double* sg,
+                                              const double* yb, double delta, double c03, double c04);
+
 __global__ __launch_bounds__(WAVE) void nmpc_kkt_kernel(const Params* __restrict__ prm, int B, KktIO io) {
   __shared__ __attribute__((aligned(16))) double smem[K_TOTAL];
   const int b = blockIdx.x;
@@ -85,7 +92,6 @@ __global__ __launch_bounds__(WAVE) void nmpc_kkt_kernel(const Params* __restrict
   LDS double* dX = sm + K_DX;
   const int N = S.N, m = S.m, nb = S.nb, nw = S.nw, ng = S.ng, nwE = S.nwE, nuE = S.nuE;
   const int nxE = prm->nxE, nXE = nxE * (N + 1);
-  const double T = S.T;
   const int lane = S.lanef();
   const double* yb = io.lam_g ? io.lam_g + (long long)b * io.ld_lam_g : nullptr;
   const double* xb = io.x + (long long)b * io.ld_x;
@@ -108,27 +114,8 @@ __global__ __launch_bounds__(WAVE) void nmpc_kkt_kernel(const Params* __restrict
     if (io.info && lane == 0) io.info[b] = verdict;
   };
 
-  // ---------------- scenario data (as nmpc_products_kernel loads it)
-  if (lane < PH_COUNT) S.stamps[lane] = 0.0;
-  for (int i = lane; i < prm->np; i += WAVE) {
-    const int e = ext_p(prm, i);
-    S.pp[i] = e >= 0 ? io.p[(long long)b * io.ld_p + e] : 0.0;
-  }
-  sync();
-  if (lane < NMPC_MAX_OBS) {
-    const bool on = lane < S.nobs;
-    S.obx[lane] = on ? (prm->oxp[lane] >= 0 ? S.pp[prm->oxp[lane]] : prm->ox[lane]) : 0.0;
-    S.oby[lane] = on ? (prm->oyp[lane] >= 0 ? S.pp[prm->oyp[lane]] : prm->oy[lane]) : 0.0;
-  }
-  if (lane == 0) {
-    S.rvars[30] = prm->w1p >= 0 ? S.pp[prm->w1p] : prm->w1;
-    S.rvars[31] = prm->w2p >= 0 ? S.pp[prm->w2p] : prm->w2;
-  }
-  for (int i = lane; i < nw; i += WAVE) {
-    const int e = ext_u(prm, i);
-    S.U[i] = e >= 0 ? xb[e] : 0.0;
-  }
-  for (int r = lane; r < ng; r += WAVE) S.dc[r] = 1.0;  // unscaled rows
+  // ---------------- scenario data
+  point_load(S, prm, lane, io.p + (long long)b * io.ld_p, xb);
 
   // ---------------- the weights: sigma_x (lane k: its stage's controls, +inf = fixed), sigma_s
   bool bad = !(delta >= 0.0) || delta == INFINITY;
@@ -167,61 +154,7 @@ __global__ __launch_bounds__(WAVE) void nmpc_kkt_kernel(const Params* __restrict
 
   // ---------------- lane k: the stage summary (Solver::assemble's Newton mode, D = sigma_s + delta)
   const int k = lane;
-  if (k <= N) {
-    double Q[36];
-#pragma unroll
-    for (int t = 0; t < 36; ++t) Q[t] = 0.0;
-    double s03 = 0.0, s04 = 0.0;
-    if (k >= 1) {  // the stages whose state depends on w
-      const LDS double* xk = S.X + k * 8;
-      double Qxy0 = 0, Qxy1 = 0, Qxy2 = 0;
-      double Qb[5] = {0, 0, 0, 0, 0};
-      for (int i = 0; i < m; ++i) {
-        const int r = k * m + i;
-        const double w = (ssb ? ssb[r] : 0.0) + delta;
-        if (i < nb) {
-          Qb[i] = w;
-        } else {
-          const double C = yb ? yb[r] : 0.0;
-          const int o = i - nb;
-          const double ddx = xk[0] - S.obx[o], ddy = xk[1] - S.oby[o];
-          const double idd = rsq(ddx * ddx + ddy * ddy);
-          const double gx = -(ddx * idd), gy = -(ddy * idd);
-          const double id3 = idd * idd * idd;
-          Qxy0 += w * gx * gx + C * (-ddy * ddy * id3);
-          Qxy1 += w * gx * gy + C * (ddx * ddy * id3);
-          Qxy2 += w * gy * gy + C * (-ddx * ddx * id3);
-        }
-      }
-      const int sv[6] = {0, 1, 2, 5, 6, 7};
-#pragma unroll
-      for (int a = 0; a < 6; ++a) {
-#pragma unroll
-        for (int bq = a; bq < 6; ++bq) Q[S.pk8(sv[a], sv[bq])] += io.obj_factor * S.Hl[k * 21 + hp(a, bq)];
-      }
-      Q[S.pk8(0, 0)] += Qxy0; Q[S.pk8(0, 1)] += Qxy1; Q[S.pk8(1, 1)] += Qxy2;
-      Q[S.pk8(2, 2)] += Qb[0]; Q[S.pk8(3, 3)] += Qb[1]; Q[S.pk8(5, 5)] += Qb[2];
-      Q[S.pk8(6, 6)] += Qb[3]; Q[S.pk8(7, 7)] += Qb[4];
-      if (k < N) {  // second derivatives of lam_{k+1}^T T f(x_k, u_k)
-        const LDS double* tg = S.trig + k * 8;
-        const double ct = tg[0], stt = tg[1], cp = tg[2], sp = tg[3], v = tg[4];
-        const LDS double* ln = S.lam + (k + 1) * 8;
-        const double l0 = ln[0], l1 = ln[1], l2 = ln[2];
-        Q[S.pk8(3, 3)] += T * (-l0 * v * cp * ct - l1 * v * sp * ct - l2 * v * stt);
-        Q[S.pk8(4, 4)] += T * (-l0 * v * cp * ct - l1 * v * sp * ct);
-        Q[S.pk8(3, 4)] += T * (l0 * v * sp * stt - l1 * v * cp * stt);
-        s03 = T * (-l0 * cp * stt - l1 * sp * stt + l2 * ct);
-        s04 = T * (-l0 * sp * ct + l1 * cp * ct);
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 36; ++t) S.Qs[k * 36 + t] = Q[t];
-    LDS double* qo = S.qs + k * 10;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) qo[c] = 0.0;
-    qo[8] = s03;
-    qo[9] = s04;
-  }
+  point_summary(S, k, io.obj_factor, ssb, yb, delta, 0.0, 0.0);
   sync();
 
   // ---------------- factorisation and inertia (zero linear terms)

@@ -6149,57 +6149,127 @@ int nmpc_adjoint_products_batch(nmpc_handle* h, int32_t B, int32_t na, const dou
   return NMPC_OK;
 }
 
-// ---- reverse-mode sensitivity of a solution in one launch (kernel: nmpc_solve_adjoint.hip)
-struct SadjArgs {
-  // x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, x_bar, lam_g_bar, X_bar
+// ---- the kernels at a solve's point (x*, lam_g*, lam_x*): the reverse-mode sensitivity
+// (nmpc_solve_adjoint.hip), the forward-mode sensitivity (nmpc_solve_tangent.hip) and the feedback
+// policy (nmpc_solve_policy.hip).  One argument block, one check, one enqueue and one staging
+// routine serve the three entry-point pairs
+struct PointArgs {
+  // x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, then the entry point's own inputs
   const double* in[12];
   int64_t ld[12];
-  double *pbar, *q, *jq;
+  int nin;
+  // the entry point's double outputs, delta last
+  double* out[6];
+  int nout;
   int32_t* info;
-  double* delta;
+  int32_t n;  // seeds or directions
+  // filled by point_check: the vector length each input's leading dimension must cover, and the
+  // per-scenario length of each output
+  size_t vlen[12], olen[6];
 };
-// the vector length each input's leading dimension must cover
-static void sadj_lengths(const Params& P, int32_t na, size_t vlen[12]) {
-  const size_t nw = P.nwE, ng = P.ng, np = P.npE, nX = (size_t)P.nxE * (P.N + 1);
-  const size_t v[12] = {nw, np, ng, nw, ng, nw, nw, ng, ng, nw * (size_t)na, ng * (size_t)na, nX * (size_t)na};
-  for (int i = 0; i < 12; ++i) vlen[i] = v[i];
-}
-// the argument checks of both entry points: nothing here touches the device
-static int sadj_check(const nmpc_handle* h, int32_t B, int32_t na, const SadjArgs& a) {
+// fills the entry point's IO block from checked arguments (DEVICE pointers) and launches
+typedef int (*PointLaunch)(const nmpc_handle* h, int32_t B, const PointArgs& a, void* stream);
+
+// the argument checks of an entry-point pair, in the order of their messages: nothing here
+// touches the device.  count_err and own_err are the entry point's own rules (null: met);
+// inputs 0 .. nreq - 1 are required apart from g; own_lengths fills vlen from 9 on and olen
+static int point_check(const nmpc_handle* h, int32_t B, const char* count_err, PointArgs& a, int nreq,
+                       const char* req_err, const char* own_err, void (*own_lengths)(const Params&, PointArgs&)) {
   if (!h) return fail(NMPC_E_INVALID, "null handle");
   if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
-  if (na <= 0) return fail(NMPC_E_INVALID, "na <= 0");
-  for (int i = 0; i < 9; ++i)
-    if (i != 4 && !a.in[i])
-      return fail(NMPC_E_INVALID, "required pointer is null (x, p, lam_g, lam_x, lbx, ubx, lbg, ubg)");
-  if (!a.in[9] && !a.in[10] && !a.in[11])
-    return fail(NMPC_E_INVALID, "every seed pointer is null (x_bar, lam_g_bar, X_bar)");
-  if (!a.pbar && !a.q) return fail(NMPC_E_INVALID, "both pbar_out and q_out are null");
-  size_t vlen[12];
-  sadj_lengths(h->hp, na, vlen);
-  for (int i = 0; i < 12; ++i)
-    if (a.in[i] && a.ld[i] != 0 && a.ld[i] < (int64_t)vlen[i])
+  if (count_err) return fail(NMPC_E_INVALID, count_err);
+  for (int i = 0; i < nreq; ++i)
+    if (i != 4 && !a.in[i]) return fail(NMPC_E_INVALID, req_err);
+  if (own_err) return fail(NMPC_E_INVALID, own_err);
+  const Params& P = h->hp;
+  const size_t nw = P.nwE, ng = P.ng, np = P.npE;
+  const size_t v[9] = {nw, np, ng, nw, ng, nw, nw, ng, ng};
+  for (int i = 0; i < 9; ++i) a.vlen[i] = v[i];
+  own_lengths(P, a);
+  for (int i = 0; i < a.nin; ++i)
+    if (a.in[i] && a.ld[i] != 0 && a.ld[i] < (int64_t)a.vlen[i])
       return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
   return NMPC_OK;
 }
-// checked arguments, DEVICE pointers: workspace from the handle (sized like a solve's, grown
-// only when it does not cover B yet), then one launch
-static int sadj_enqueue(nmpc_handle* h, int32_t B, int32_t na, const SadjArgs& a, void* stream) {
-  const int per = h->ws_doubles > kSadjWs ? h->ws_doubles : kSadjWs;
-  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
-  SadjIO io;
+// the kernels' common argument block
+static PointIO point_io(const nmpc_handle* h, const PointArgs& a) {
+  PointIO io;
   io.x = a.in[0]; io.p = a.in[1]; io.lam_g = a.in[2]; io.lam_x = a.in[3]; io.g = a.in[4];
   io.lbx = a.in[5]; io.ubx = a.in[6]; io.lbg = a.in[7]; io.ubg = a.in[8];
-  io.x_bar = a.in[9]; io.lam_g_bar = a.in[10]; io.X_bar = a.in[11];
   io.ld_x = a.ld[0]; io.ld_p = a.ld[1]; io.ld_lam_g = a.ld[2]; io.ld_lam_x = a.ld[3]; io.ld_g = a.ld[4];
   io.ld_lbx = a.ld[5]; io.ld_ubx = a.ld[6]; io.ld_lbg = a.ld[7]; io.ld_ubg = a.ld[8];
-  io.ld_x_bar = a.ld[9]; io.ld_lam_g_bar = a.ld[10]; io.ld_X_bar = a.ld[11];
-  io.na = na;
-  io.pbar = a.pbar; io.q = a.q; io.jq = a.jq; io.info = a.info; io.delta = a.delta;
+  io.info = a.info; io.delta = a.out[a.nout - 1];
   io.ws = h->dws;
-  const hipError_t e = (hipError_t)nmpc_solve_adjoint_launch(h->dprm, (int)B, io, stream);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("solve adjoint launch: ") + hipGetErrorString(e));
+  return io;
+}
+// checked arguments, DEVICE pointers: workspace from the handle (sized like a solve's, grown
+// only when it does not cover B yet), then one launch
+static int point_enqueue(nmpc_handle* h, int32_t B, const PointArgs& a, void* stream, PointLaunch launch,
+                         const char* what) {
+  const int per = h->ws_doubles > kPointWs ? h->ws_doubles : kPointWs;
+  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
+  const hipError_t e = (hipError_t)launch(h, B, a, stream);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
   return NMPC_OK;
+}
+// checked arguments, HOST pointers.  Staging: the inputs (absent ones take no room), the
+// outputs, the verdicts; H2D, one launch, sync, D2H
+static int point_staged(nmpc_handle* h, int32_t B, const PointArgs& a, PointLaunch launch, const char* what) {
+  size_t n_in[12], total = 0;
+  for (int i = 0; i < a.nin; ++i) {
+    n_in[i] = !a.in[i] ? 0 : (a.ld[i] == 0 ? a.vlen[i] : (size_t)(B - 1) * (size_t)a.ld[i] + a.vlen[i]);
+    total += n_in[i];
+  }
+  for (int i = 0; i < a.nout; ++i) total += a.out[i] ? (size_t)B * a.olen[i] : 0;
+  total += a.info ? ((size_t)B + 1) / 2 : 0;  // B int32 in whole doubles
+  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
+  double* q = h->dbuf;
+  PointArgs d = a;
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < a.nin; ++i) {
+    d.in[i] = a.in[i] ? q : nullptr;
+    if (a.in[i] && e == hipSuccess) e = hipMemcpy(q, a.in[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
+    q += n_in[i];
+  }
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
+  for (int i = 0; i < a.nout; ++i) {
+    d.out[i] = a.out[i] ? q : nullptr;
+    q += a.out[i] ? (size_t)B * a.olen[i] : 0;
+  }
+  d.info = a.info ? (int32_t*)q : nullptr;
+  if (int rc = point_enqueue(h, B, d, nullptr, launch, what)) return rc;
+  e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
+  for (int i = 0; i < a.nout; ++i)
+    if (a.out[i] && e == hipSuccess)
+      e = hipMemcpy(a.out[i], d.out[i], (size_t)B * a.olen[i] * sizeof(double), hipMemcpyDeviceToHost);
+  if (a.info && e == hipSuccess) e = hipMemcpy(a.info, d.info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
+// ---- reverse-mode sensitivity of a solution in one launch (kernel: nmpc_solve_adjoint.hip)
+// own inputs x_bar, lam_g_bar, X_bar; outputs pbar, q, jq, delta
+static int sadj_check(const nmpc_handle* h, int32_t B, PointArgs& a) {
+  const char* own = nullptr;
+  if (!a.in[9] && !a.in[10] && !a.in[11]) own = "every seed pointer is null (x_bar, lam_g_bar, X_bar)";
+  else if (!a.out[0] && !a.out[1]) own = "both pbar_out and q_out are null";
+  return point_check(h, B, a.n <= 0 ? "na <= 0" : nullptr, a, 9,
+                     "required pointer is null (x, p, lam_g, lam_x, lbx, ubx, lbg, ubg)", own,
+                     [](const Params& P, PointArgs& a) {
+                       const size_t nw = P.nwE, ng = P.ng, np = P.npE, nX = (size_t)P.nxE * (P.N + 1), na = a.n;
+                       a.vlen[9] = nw * na; a.vlen[10] = ng * na; a.vlen[11] = nX * na;
+                       a.olen[0] = np * na; a.olen[1] = nw * na; a.olen[2] = ng * na; a.olen[3] = 1;
+                     });
+}
+static int sadj_launch(const nmpc_handle* h, int32_t B, const PointArgs& a, void* stream) {
+  SadjIO io;
+  io.pt = point_io(h, a);
+  io.x_bar = a.in[9]; io.lam_g_bar = a.in[10]; io.X_bar = a.in[11];
+  io.ld_x_bar = a.ld[9]; io.ld_lam_g_bar = a.ld[10]; io.ld_X_bar = a.ld[11];
+  io.na = a.n;
+  io.pbar = a.out[0]; io.q = a.out[1]; io.jq = a.out[2];
+  return nmpc_solve_adjoint_launch(h->dprm, (int)B, io, stream);
 }
 
 int nmpc_solve_adjoint_batch_dev(nmpc_handle* h, int32_t B, int32_t na, const double* x, int64_t ld_x,
@@ -6210,12 +6280,12 @@ int nmpc_solve_adjoint_batch_dev(nmpc_handle* h, int32_t B, int32_t na, const do
                                  const double* x_bar, int64_t ld_x_bar, const double* lam_g_bar,
                                  int64_t ld_lam_g_bar, const double* X_bar, int64_t ld_X_bar, double* pbar_out,
                                  double* q_out, double* jq_out, int32_t* info_out, double* delta_out, void* stream) {
-  const SadjArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, x_bar, lam_g_bar, X_bar},
-                   {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_x_bar, ld_lam_g_bar,
-                    ld_X_bar},
-                   pbar_out, q_out, jq_out, info_out, delta_out};
-  if (int rc = sadj_check(h, B, na, a)) return rc;
-  return sadj_enqueue(h, B, na, a, stream);
+  PointArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, x_bar, lam_g_bar, X_bar},
+              {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_x_bar, ld_lam_g_bar,
+               ld_X_bar},
+              12, {pbar_out, q_out, jq_out, delta_out}, 4, info_out, na};
+  if (int rc = sadj_check(h, B, a)) return rc;
+  return point_enqueue(h, B, a, stream, sadj_launch, "solve adjoint");
 }
 
 int nmpc_solve_adjoint_batch(nmpc_handle* h, int32_t B, int32_t na, const double* x, int64_t ld_x, const double* p,
@@ -6226,98 +6296,35 @@ int nmpc_solve_adjoint_batch(nmpc_handle* h, int32_t B, int32_t na, const double
                              const double* lam_g_bar, int64_t ld_lam_g_bar, const double* X_bar, int64_t ld_X_bar,
                              double* pbar_out, double* q_out, double* jq_out, int32_t* info_out,
                              double* delta_out) {
-  const SadjArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, x_bar, lam_g_bar, X_bar},
-                   {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_x_bar, ld_lam_g_bar,
-                    ld_X_bar},
-                   pbar_out, q_out, jq_out, info_out, delta_out};
-  if (int rc = sadj_check(h, B, na, a)) return rc;
-  const Params& P = h->hp;
-  // staging: the twelve inputs (absent ones take no room), the three outputs, delta, the verdicts
-  size_t vlen[12], n_in[12], total = 0;
-  sadj_lengths(P, na, vlen);
-  double* hout[4] = {pbar_out, q_out, jq_out, delta_out};
-  const size_t olen[4] = {(size_t)P.npE * na, (size_t)P.nwE * na, (size_t)P.ng * na, 1};
-  for (int i = 0; i < 12; ++i) {
-    n_in[i] = !a.in[i] ? 0 : (a.ld[i] == 0 ? vlen[i] : (size_t)(B - 1) * (size_t)a.ld[i] + vlen[i]);
-    total += n_in[i];
-  }
-  for (int i = 0; i < 4; ++i) total += hout[i] ? (size_t)B * olen[i] : 0;
-  total += info_out ? ((size_t)B + 1) / 2 : 0;  // B int32 in whole doubles
-  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
-  double* q = h->dbuf;
-  SadjArgs d = a;
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 12; ++i) {
-    d.in[i] = a.in[i] ? q : nullptr;
-    if (a.in[i] && e == hipSuccess) e = hipMemcpy(q, a.in[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
-    q += n_in[i];
-  }
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
-  double* dout[4];
-  for (int i = 0; i < 4; ++i) {
-    dout[i] = hout[i] ? q : nullptr;
-    q += hout[i] ? (size_t)B * olen[i] : 0;
-  }
-  d.pbar = dout[0]; d.q = dout[1]; d.jq = dout[2]; d.delta = dout[3];
-  d.info = info_out ? (int32_t*)q : nullptr;
-  if (int rc = sadj_enqueue(h, B, na, d, nullptr)) return rc;
-  e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
-  for (int i = 0; i < 4; ++i)
-    if (hout[i] && e == hipSuccess)
-      e = hipMemcpy(hout[i], dout[i], (size_t)B * olen[i] * sizeof(double), hipMemcpyDeviceToHost);
-  if (info_out && e == hipSuccess) e = hipMemcpy(info_out, d.info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
-  return NMPC_OK;
+  PointArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, x_bar, lam_g_bar, X_bar},
+              {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_x_bar, ld_lam_g_bar,
+               ld_X_bar},
+              12, {pbar_out, q_out, jq_out, delta_out}, 4, info_out, na};
+  if (int rc = sadj_check(h, B, a)) return rc;
+  return point_staged(h, B, a, sadj_launch, "solve adjoint");
 }
 
-// ---- forward-mode sensitivity of a solution in one launch (kernel: nmpc_solve_tangent.hip)
-struct StanArgs {
-  // x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp
-  const double* in[10];
-  int64_t ld[10];
-  double *dx, *dlam_g, *dX;
-  int32_t* info;
-  double* delta;
-};
-// the vector length each input's leading dimension must cover
-static void stan_lengths(const Params& P, int32_t nd, size_t vlen[10]) {
-  const size_t nw = P.nwE, ng = P.ng, np = P.npE;
-  const size_t v[10] = {nw, np, ng, nw, ng, nw, nw, ng, ng, np * (size_t)nd};
-  for (int i = 0; i < 10; ++i) vlen[i] = v[i];
+// ---- forward-mode sensitivity of a solution in one launch (kernel: nmpc_solve_tangent.hip) and
+// the plan's feedback policy in one launch (kernel: nmpc_solve_policy.hip): own input dp
+static void dp_length(const Params& P, PointArgs& a) { a.vlen[9] = (size_t)P.npE * (size_t)a.n; }
+// outputs dx, dlam_g, dX, delta
+static int stan_check(const nmpc_handle* h, int32_t B, PointArgs& a) {
+  return point_check(h, B, a.n <= 0 ? "nd <= 0" : nullptr, a, 10,
+                     "required pointer is null (x, p, lam_g, lam_x, lbx, ubx, lbg, ubg, dp)",
+                     !a.out[0] && !a.out[1] && !a.out[2] ? "dx_out, dlam_g_out and dX_out are all null" : nullptr,
+                     [](const Params& P, PointArgs& a) {
+                       const size_t nd = a.n;
+                       dp_length(P, a);
+                       a.olen[0] = P.nwE * nd; a.olen[1] = P.ng * nd; a.olen[2] = (size_t)P.nxE * (P.N + 1) * nd;
+                       a.olen[3] = 1;
+                     });
 }
-// the argument checks of both entry points: nothing here touches the device
-static int stan_check(const nmpc_handle* h, int32_t B, int32_t nd, const StanArgs& a) {
-  if (!h) return fail(NMPC_E_INVALID, "null handle");
-  if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
-  if (nd <= 0) return fail(NMPC_E_INVALID, "nd <= 0");
-  for (int i = 0; i < 10; ++i)
-    if (i != 4 && !a.in[i])
-      return fail(NMPC_E_INVALID, "required pointer is null (x, p, lam_g, lam_x, lbx, ubx, lbg, ubg, dp)");
-  if (!a.dx && !a.dlam_g && !a.dX) return fail(NMPC_E_INVALID, "dx_out, dlam_g_out and dX_out are all null");
-  size_t vlen[10];
-  stan_lengths(h->hp, nd, vlen);
-  for (int i = 0; i < 10; ++i)
-    if (a.in[i] && a.ld[i] != 0 && a.ld[i] < (int64_t)vlen[i])
-      return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
-  return NMPC_OK;
-}
-// checked arguments, DEVICE pointers: workspace from the handle (sized like a solve's, grown
-// only when it does not cover B yet), then one launch
-static int stan_enqueue(nmpc_handle* h, int32_t B, int32_t nd, const StanArgs& a, void* stream) {
-  const int per = h->ws_doubles > kStanWs ? h->ws_doubles : kStanWs;
-  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
+static int stan_launch(const nmpc_handle* h, int32_t B, const PointArgs& a, void* stream) {
   StanIO io;
-  io.x = a.in[0]; io.p = a.in[1]; io.lam_g = a.in[2]; io.lam_x = a.in[3]; io.g = a.in[4];
-  io.lbx = a.in[5]; io.ubx = a.in[6]; io.lbg = a.in[7]; io.ubg = a.in[8]; io.dp = a.in[9];
-  io.ld_x = a.ld[0]; io.ld_p = a.ld[1]; io.ld_lam_g = a.ld[2]; io.ld_lam_x = a.ld[3]; io.ld_g = a.ld[4];
-  io.ld_lbx = a.ld[5]; io.ld_ubx = a.ld[6]; io.ld_lbg = a.ld[7]; io.ld_ubg = a.ld[8]; io.ld_dp = a.ld[9];
-  io.nd = nd;
-  io.dx = a.dx; io.dlam_g = a.dlam_g; io.dX = a.dX; io.info = a.info; io.delta = a.delta;
-  io.ws = h->dws;
-  const hipError_t e = (hipError_t)nmpc_solve_tangent_launch(h->dprm, (int)B, io, stream);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("solve tangent launch: ") + hipGetErrorString(e));
-  return NMPC_OK;
+  io.pt = point_io(h, a);
+  io.dp = a.in[9]; io.ld_dp = a.ld[9]; io.nd = a.n;
+  io.dx = a.out[0]; io.dlam_g = a.out[1]; io.dX = a.out[2];
+  return nmpc_solve_tangent_launch(h->dprm, (int)B, io, stream);
 }
 
 int nmpc_solve_tangent_batch_dev(nmpc_handle* h, int32_t B, int32_t nd, const double* x, int64_t ld_x,
@@ -6327,11 +6334,11 @@ int nmpc_solve_tangent_batch_dev(nmpc_handle* h, int32_t B, int32_t nd, const do
                                  const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg,
                                  const double* dp, int64_t ld_dp, double* dx_out, double* dlam_g_out,
                                  double* dX_out, int32_t* info_out, double* delta_out, void* stream) {
-  const StanArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
-                   {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp},
-                   dx_out, dlam_g_out, dX_out, info_out, delta_out};
-  if (int rc = stan_check(h, B, nd, a)) return rc;
-  return stan_enqueue(h, B, nd, a, stream);
+  PointArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
+              {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp}, 10,
+              {dx_out, dlam_g_out, dX_out, delta_out}, 4, info_out, nd};
+  if (int rc = stan_check(h, B, a)) return rc;
+  return point_enqueue(h, B, a, stream, stan_launch, "solve tangent");
 }
 
 int nmpc_solve_tangent_batch(nmpc_handle* h, int32_t B, int32_t nd, const double* x, int64_t ld_x, const double* p,
@@ -6340,101 +6347,34 @@ int nmpc_solve_tangent_batch(nmpc_handle* h, int32_t B, int32_t nd, const double
                              const double* ubx, int64_t ld_ubx, const double* lbg, int64_t ld_lbg,
                              const double* ubg, int64_t ld_ubg, const double* dp, int64_t ld_dp, double* dx_out,
                              double* dlam_g_out, double* dX_out, int32_t* info_out, double* delta_out) {
-  const StanArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
-                   {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp},
-                   dx_out, dlam_g_out, dX_out, info_out, delta_out};
-  if (int rc = stan_check(h, B, nd, a)) return rc;
-  const Params& P = h->hp;
-  // staging: the ten inputs (absent ones take no room), the three outputs, delta, the verdicts
-  size_t vlen[10], n_in[10], total = 0;
-  stan_lengths(P, nd, vlen);
-  double* hout[4] = {dx_out, dlam_g_out, dX_out, delta_out};
-  const size_t olen[4] = {(size_t)P.nwE * nd, (size_t)P.ng * nd, (size_t)P.nxE * (P.N + 1) * nd, 1};
-  for (int i = 0; i < 10; ++i) {
-    n_in[i] = !a.in[i] ? 0 : (a.ld[i] == 0 ? vlen[i] : (size_t)(B - 1) * (size_t)a.ld[i] + vlen[i]);
-    total += n_in[i];
-  }
-  for (int i = 0; i < 4; ++i) total += hout[i] ? (size_t)B * olen[i] : 0;
-  total += info_out ? ((size_t)B + 1) / 2 : 0;  // B int32 in whole doubles
-  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
-  double* q = h->dbuf;
-  StanArgs d = a;
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 10; ++i) {
-    d.in[i] = a.in[i] ? q : nullptr;
-    if (a.in[i] && e == hipSuccess) e = hipMemcpy(q, a.in[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
-    q += n_in[i];
-  }
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
-  double* dout[4];
-  for (int i = 0; i < 4; ++i) {
-    dout[i] = hout[i] ? q : nullptr;
-    q += hout[i] ? (size_t)B * olen[i] : 0;
-  }
-  d.dx = dout[0]; d.dlam_g = dout[1]; d.dX = dout[2]; d.delta = dout[3];
-  d.info = info_out ? (int32_t*)q : nullptr;
-  if (int rc = stan_enqueue(h, B, nd, d, nullptr)) return rc;
-  e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
-  for (int i = 0; i < 4; ++i)
-    if (hout[i] && e == hipSuccess)
-      e = hipMemcpy(hout[i], dout[i], (size_t)B * olen[i] * sizeof(double), hipMemcpyDeviceToHost);
-  if (info_out && e == hipSuccess) e = hipMemcpy(info_out, d.info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
-  return NMPC_OK;
+  PointArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
+              {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp}, 10,
+              {dx_out, dlam_g_out, dX_out, delta_out}, 4, info_out, nd};
+  if (int rc = stan_check(h, B, a)) return rc;
+  return point_staged(h, B, a, stan_launch, "solve tangent");
 }
 
-// ---- the plan's feedback policy in one launch (kernel: nmpc_solve_policy.hip)
-struct SpolArgs {
-  // x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp
-  const double* in[10];
-  int64_t ld[10];
-  // K, kff, A, B, X, delta
-  double* out[6];
-  int32_t* info;
-};
-// per-scenario lengths of the six double outputs
-static void spol_out_lengths(const Params& P, int32_t nd, size_t olen[6]) {
-  const size_t nu = P.nuE, nx = P.nxE, N = P.N;
-  const size_t v[6] = {nu * nx * N, (size_t)P.nwE * (size_t)nd, nx * nx * N, nx * nu * N, nx * (N + 1), 1};
-  for (int i = 0; i < 6; ++i) olen[i] = v[i];
+// outputs K, kff, A, B, X, delta
+static int spol_check(const nmpc_handle* h, int32_t B, PointArgs& a) {
+  const char* own = nullptr;
+  if (a.n > 0 && !a.in[9]) own = "dp is null with nd > 0";
+  else if (a.n == 0 && (a.in[9] || a.out[1])) own = "dp and kff_out must be null with nd = 0";
+  else if (!a.out[0] && !a.out[1] && !a.out[2] && !a.out[3]) own = "K_out, kff_out, A_out and B_out are all null";
+  return point_check(h, B, a.n < 0 ? "nd < 0" : nullptr, a, 9,
+                     "required pointer is null (x, p, lam_g, lam_x, lbx, ubx, lbg, ubg)", own,
+                     [](const Params& P, PointArgs& a) {
+                       const size_t nu = P.nuE, nx = P.nxE, N = P.N;
+                       dp_length(P, a);
+                       a.olen[0] = nu * nx * N; a.olen[1] = (size_t)P.nwE * (size_t)a.n; a.olen[2] = nx * nx * N;
+                       a.olen[3] = nx * nu * N; a.olen[4] = nx * (N + 1); a.olen[5] = 1;
+                     });
 }
-// the argument checks of both entry points: nothing here touches the device
-static int spol_check(const nmpc_handle* h, int32_t B, int32_t nd, const SpolArgs& a) {
-  if (!h) return fail(NMPC_E_INVALID, "null handle");
-  if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
-  if (nd < 0) return fail(NMPC_E_INVALID, "nd < 0");
-  for (int i = 0; i < 9; ++i)
-    if (i != 4 && !a.in[i])
-      return fail(NMPC_E_INVALID, "required pointer is null (x, p, lam_g, lam_x, lbx, ubx, lbg, ubg)");
-  if (nd > 0 && !a.in[9]) return fail(NMPC_E_INVALID, "dp is null with nd > 0");
-  if (nd == 0 && (a.in[9] || a.out[1])) return fail(NMPC_E_INVALID, "dp and kff_out must be null with nd = 0");
-  if (!a.out[0] && !a.out[1] && !a.out[2] && !a.out[3])
-    return fail(NMPC_E_INVALID, "K_out, kff_out, A_out and B_out are all null");
-  size_t vlen[10];
-  stan_lengths(h->hp, nd, vlen);
-  for (int i = 0; i < 10; ++i)
-    if (a.in[i] && a.ld[i] != 0 && a.ld[i] < (int64_t)vlen[i])
-      return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
-  return NMPC_OK;
-}
-// checked arguments, DEVICE pointers: workspace from the handle (sized like a solve's, grown
-// only when it does not cover B yet), then one launch
-static int spol_enqueue(nmpc_handle* h, int32_t B, int32_t nd, const SpolArgs& a, void* stream) {
-  const int per = h->ws_doubles > kSpolWs ? h->ws_doubles : kSpolWs;
-  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
+static int spol_launch(const nmpc_handle* h, int32_t B, const PointArgs& a, void* stream) {
   SpolIO io;
-  io.x = a.in[0]; io.p = a.in[1]; io.lam_g = a.in[2]; io.lam_x = a.in[3]; io.g = a.in[4];
-  io.lbx = a.in[5]; io.ubx = a.in[6]; io.lbg = a.in[7]; io.ubg = a.in[8]; io.dp = a.in[9];
-  io.ld_x = a.ld[0]; io.ld_p = a.ld[1]; io.ld_lam_g = a.ld[2]; io.ld_lam_x = a.ld[3]; io.ld_g = a.ld[4];
-  io.ld_lbx = a.ld[5]; io.ld_ubx = a.ld[6]; io.ld_lbg = a.ld[7]; io.ld_ubg = a.ld[8]; io.ld_dp = a.ld[9];
-  io.nd = nd;
-  io.K = a.out[0]; io.kff = a.out[1]; io.A = a.out[2]; io.Bm = a.out[3]; io.X = a.out[4]; io.delta = a.out[5];
-  io.info = a.info;
-  io.ws = h->dws;
-  const hipError_t e = (hipError_t)nmpc_solve_policy_launch(h->dprm, (int)B, io, stream);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("solve policy launch: ") + hipGetErrorString(e));
-  return NMPC_OK;
+  io.pt = point_io(h, a);
+  io.dp = a.in[9]; io.ld_dp = a.ld[9]; io.nd = a.n;
+  io.K = a.out[0]; io.kff = a.out[1]; io.A = a.out[2]; io.Bm = a.out[3]; io.X = a.out[4];
+  return nmpc_solve_policy_launch(h->dprm, (int)B, io, stream);
 }
 
 int nmpc_solve_policy_batch_dev(nmpc_handle* h, int32_t B, int32_t nd, const double* x, int64_t ld_x,
@@ -6444,11 +6384,11 @@ int nmpc_solve_policy_batch_dev(nmpc_handle* h, int32_t B, int32_t nd, const dou
                                 const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg,
                                 const double* dp, int64_t ld_dp, double* K_out, double* kff_out, double* A_out,
                                 double* B_out, double* X_out, int32_t* info_out, double* delta_out, void* stream) {
-  const SpolArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
-                   {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp},
-                   {K_out, kff_out, A_out, B_out, X_out, delta_out}, info_out};
-  if (int rc = spol_check(h, B, nd, a)) return rc;
-  return spol_enqueue(h, B, nd, a, stream);
+  PointArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
+              {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp}, 10,
+              {K_out, kff_out, A_out, B_out, X_out, delta_out}, 6, info_out, nd};
+  if (int rc = spol_check(h, B, a)) return rc;
+  return point_enqueue(h, B, a, stream, spol_launch, "solve policy");
 }
 
 int nmpc_solve_policy_batch(nmpc_handle* h, int32_t B, int32_t nd, const double* x, int64_t ld_x, const double* p,
@@ -6458,45 +6398,11 @@ int nmpc_solve_policy_batch(nmpc_handle* h, int32_t B, int32_t nd, const double*
                             const double* ubg, int64_t ld_ubg, const double* dp, int64_t ld_dp, double* K_out,
                             double* kff_out, double* A_out, double* B_out, double* X_out, int32_t* info_out,
                             double* delta_out) {
-  const SpolArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
-                   {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp},
-                   {K_out, kff_out, A_out, B_out, X_out, delta_out}, info_out};
-  if (int rc = spol_check(h, B, nd, a)) return rc;
-  const Params& P = h->hp;
-  // staging: the ten inputs (absent ones take no room), the six outputs, the verdicts
-  size_t vlen[10], n_in[10], olen[6], total = 0;
-  stan_lengths(P, nd, vlen);
-  spol_out_lengths(P, nd, olen);
-  for (int i = 0; i < 10; ++i) {
-    n_in[i] = !a.in[i] ? 0 : (a.ld[i] == 0 ? vlen[i] : (size_t)(B - 1) * (size_t)a.ld[i] + vlen[i]);
-    total += n_in[i];
-  }
-  for (int i = 0; i < 6; ++i) total += a.out[i] ? (size_t)B * olen[i] : 0;
-  total += info_out ? ((size_t)B + 1) / 2 : 0;  // B int32 in whole doubles
-  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
-  double* q = h->dbuf;
-  SpolArgs d = a;
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 10; ++i) {
-    d.in[i] = a.in[i] ? q : nullptr;
-    if (a.in[i] && e == hipSuccess) e = hipMemcpy(q, a.in[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
-    q += n_in[i];
-  }
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
-  for (int i = 0; i < 6; ++i) {
-    d.out[i] = a.out[i] ? q : nullptr;
-    q += a.out[i] ? (size_t)B * olen[i] : 0;
-  }
-  d.info = info_out ? (int32_t*)q : nullptr;
-  if (int rc = spol_enqueue(h, B, nd, d, nullptr)) return rc;
-  e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
-  for (int i = 0; i < 6; ++i)
-    if (a.out[i] && e == hipSuccess)
-      e = hipMemcpy(a.out[i], d.out[i], (size_t)B * olen[i] * sizeof(double), hipMemcpyDeviceToHost);
-  if (info_out && e == hipSuccess) e = hipMemcpy(info_out, d.info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
-  return NMPC_OK;
+  PointArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
+              {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp}, 10,
+              {K_out, kff_out, A_out, B_out, X_out, delta_out}, 6, info_out, nd};
+  if (int rc = spol_check(h, B, a)) return rc;
+  return point_staged(h, B, a, spol_launch, "solve policy");
 }
 
 int nmpc_shift_dev(nmpc_handle* h, int32_t B, double* p, int64_t ld_p, const double* u_sol, double* w_out,

@@ -9,33 +9,24 @@
 // Solver.sensitivity_adjoint composes on the host from three launches of nmpc_adjoint.hip and
 // nmpc_kkt.hip, the weights in NumPy and the delta ladder as a Python loop, on the device.
 //
-// Part of the evaluation kernel's translation unit (nmpc_eval.hip includes this file last), so
-// everything is the text the solver compiles: Solver::rollout, stage_cost, row_value,
-// derivs<true, true>, adjoint, riccati, resolve, forward, row_jd, stage_AB, grad_u, and the
-// curvature expressions of nmpc_kkt.hip / nmpc_adjoint.hip.
+// Part of the evaluation kernel's translation unit (nmpc_eval.hip includes this file after
+// nmpc_point.hip), so everything is the text the solver compiles; the LDS carve-up, the
+// workspace slices and the steps up to the factorisation are nmpc_point.hip's, shared with
+// nmpc_solve_tangent.hip and nmpc_solve_policy.hip.
 //
 // Execution model: the siblings'.  One wavefront per scenario, fp64, stage k on lane k, rows
 // and variables strided over the lanes, control flow wave-uniform.
 // Once per wavefront:
-//   1. scenario data, rollout and stage costs as nmpc_kkt_kernel; where a cost weight comes from
-//      p, the unit-weight stage-cost gradients as nmpc_adjoint_kernel (formed after step 4, into
-//      the stage summaries' slice, which is dead by then); derivs<true, true> and
-//      adjoint(1, lam_g): gl, Hl, lam_{k+1} (the objective factor is 1);
-//   2. the barrier weights, Solver.barrier_weights' operations in their order:
-//        sl = max(v - lo, brf max(1, |lo|)), su = max(hi - v, brf max(1, |hi|)),
-//        sigma = max(-lam, 0) / sl + max(lam, 0) / su
-//      (max as numpy.maximum: a NaN stays); lane k its stage's controls (lbx == ubx: +inf, the
-//      variable leaves the system, Solver::fixm) and its stage's rows (v = the given g, else
-//      the kernel's own row value); an equality row, lbx > ubx or a weight that is not a
+//   1. point_load, point_rollout: scenario data, rollout and stage costs;
+//   2. point_weights: the barrier weights; an equality row, lbx > ubx or a weight that is not a
 //      finite non-negative number ends the scenario with info = -11 and NaN outputs;
+//      point_derivs: gl, Hl, lam_{k+1};
 //   3. lane k keeps the second-order data every seed's pullback needs: the summed obstacle
 //      curvature and the dynamics terms d33, d34, d44, s03, s04 of lam_{k+1}^T T f (stage 0's
 //      included: its Hxu_0 z_0 reaches the x0 block of pbar);
-//   4. the delta ladder: delta = 0, the stage summaries Q_k with D = sigma_s + delta
-//      (nmpc_kkt_kernel's text), Solver::riccati; on a failed inertia verdict the next rung
-//      (first_hessian_perturbation, then x perturb_inc_fact_first, then x perturb_inc_fact: the
-//      host ladder's multiplications) while it is <= max_hessian_perturbation; beyond it
-//      info = 1 and NaN outputs.
+//   4. point_ladder: the stage summaries and Solver::riccati up the delta ladder; beyond
+//      max_hessian_perturbation info = 1 and NaN outputs.  point_unit_grads where a cost weight
+//      comes from p.
 // Per seed (the factorisation is shared):
 //   5. r_w = x_bar + (dX/dw)^T X_bar -- with X_bar, one reverse sweep (Solver::adjoint on the
 //      stage sources X_bar_k, grad_u) -- and q_k = -G_k^T (sigma_s lam_g_bar);
@@ -49,188 +40,51 @@
 
 namespace {
 
-static_assert(CapA::L.wstotal >= kSadjWs && CapB::L.wstotal >= kSadjWs && CapC::L.wstotal >= kSadjWs &&
-                  CapD::L.wstotal >= kSadjWs && CapA32::L.wstotal >= kSadjWs && CapC32::L.wstotal >= kSadjWs &&
-                  CapE::L.wstotal >= kSadjWs,
-              "a solver class's workspace is smaller than one wavefront's of the fused sensitivity kernel");
-
-// LDS carve-up (doubles): the KKT kernel's without a buffer of its own for the state step, which
-// lives in the prefix-sum scratch: Solver::forward reads nothing there, every lane takes its
-// stage's entries into registers before the pullback's sweep uses the scratch again, and the
-// next seed's sweeps find it dead.  23.6 KB: six workgroups per CU's 160 KiB, where the KKT
-// kernel's 27.7 KB allow five
-constexpr int A_PP = 0;                       // p, internal layout (<= 64)
-constexpr int A_OB = A_PP + 64;               // obstacle x (16), y (16)
-constexpr int A_RV = A_OB + 2 * NMPC_MAX_OBS; // Solver::rvars; [30], [31] = cost weights
-constexpr int A_ST = A_RV + 32;               // phase-timer slots (NMPC_STAMPS builds write them)
-constexpr int A_X = A_ST + PH_COUNT;          // trajectory, 8 per stage
-constexpr int A_TRIG = A_X + 8 * NS;
-constexpr int A_INC = A_TRIG + 8 * NS;        // prefix / suffix sum scratch; the sweeps' P / p buffers; the
-                                              // seed's state step (dX/dw) q between forward and pullback
-constexpr int A_LAM = A_INC + 8 * NS;         // lam, then each seed's nu
-constexpr int A_QS = A_LAM + 8 * NS;          // q_k (8), S_k[0][3], S_k[0][4] per stage
-constexpr int A_SW = A_QS + 10 * NS;          // S~ (48), R~ (22), r~ (8) of the current stage
-constexpr int A_FIX = A_SW + 48 + 22 + 8;     // fixed-control masks, one int per stage
-constexpr int A_TOTAL = A_FIX + NS / 2 + 2;
-static_assert(A_TOTAL * 8 <= 32 * 1024, "fused sensitivity kernel LDS");
-
-// numpy.maximum: a NaN operand stays (fmax would drop it)
-__device__ __forceinline__ double npmax(double a, double b) { return (a != a || b != b) ? NAN : (a > b ? a : b); }
-// Solver.barrier_weights' weight of one value between its bounds
-__device__ __forceinline__ double barrier_sigma(double v, double lam, double lo, double hi, double brf) {
-  const double sl = npmax(v - lo, brf * npmax(1.0, fabs(lo)));
-  const double su = npmax(hi - v, brf * npmax(1.0, fabs(hi)));
-  return npmax(-lam, 0.0) / sl + npmax(lam, 0.0) / su;
-}
-
 __global__ __launch_bounds__(WAVE) void nmpc_solve_adjoint_kernel(const Params* __restrict__ prm, int B, SadjIO io) {
   __shared__ __attribute__((aligned(16))) double smem[A_TOTAL];
   const int b = blockIdx.x;
   if (b >= B) return;
   Solver<CapEv> S{};
   LDS double* sm = (LDS double*)smem;
-  GLB double* gw = (GLB double*)(io.ws + (long long)b * kSadjWs);
-  S.P = (const CST Params*)prm; S.sm = sm; S.lane_ = threadIdx.x; S.b = b;
-  S.N = prm->N; S.m = prm->m; S.nobs = prm->nobs; S.nw = prm->nw; S.ng = prm->ng; S.T = prm->T;
-  S.nb = prm->nb; S.nuE = prm->nuE; S.nwE = prm->nwE;
-  S.U = gw + kKktU; S.gl = gw + kKktGl; S.Hl = gw + kKktHl; S.tc = gw + kKktTc; S.dc = gw + kKktDc;
-  S.Qs = gw + kKktQs; S.K = gw + kKktK; S.Rk = gw + kKktRk; S.kf = gw + kKktKf;
-  GLB double* Rd = gw + kKktRd;  // sigma_x, the kernel's layout
-  GLB double* rv = gw + kKktRv;  // the seed's control terms
-  GLB double* dU = gw + kKktDu;  // its q
-  GLB double* sg = gw + kSadjSg; // sigma_s
-  GLB double* yv = gw + kSadjY;  // the seed's y
-  GLB double* uw = gw + kKktQs;  // after the ladder: unit-weight stage-cost gradients, 6 + 6 per stage
-  S.pp = sm + A_PP; S.obx = sm + A_OB; S.oby = S.obx + NMPC_MAX_OBS; S.rvars = sm + A_RV; S.stamps = sm + A_ST;
-  S.X = sm + A_X; S.trig = sm + A_TRIG; S.inc = sm + A_INC; S.lam = sm + A_LAM; S.qs = sm + A_QS;
-  S.Pa = S.inc; S.Pb = S.inc + 64; S.pva = S.inc + 128; S.pvb = S.inc + 136;
-  S.St = sm + A_SW; S.Rc = S.St + 48; S.Rv = S.Rc + 22;
-  S.fixm = (LDS int*)(sm + A_FIX);
+  const PointRefs R = point_bind(S, prm, sm, io.pt, b);
+  GLB double *rv = R.rv, *dU = R.dU, *sg = R.sg, *yv = R.yv, *uw = R.uw;
   LDS double* dX = sm + A_INC;
-  const int N = S.N, m = S.m, nb = S.nb, nw = S.nw, ng = S.ng, nwE = S.nwE, nuE = S.nuE;
+  const int N = S.N, m = S.m, nb = S.nb, nw = S.nw, ng = S.ng, nwE = S.nwE;
   const int np = prm->np, npE = prm->npE, nxE = prm->nxE, nXE = nxE * (N + 1);
   const int w1p = prm->w1p, w2p = prm->w2p;
   const double T = S.T;
   const int lane = S.lanef();
-  const double* xb = io.x + (long long)b * io.ld_x;
-  const double* yb = io.lam_g + (long long)b * io.ld_lam_g;
-  const double* lxb = io.lam_x + (long long)b * io.ld_lam_x;
-  const double* gb = io.g ? io.g + (long long)b * io.ld_g : nullptr;
-  const double* lbxb = io.lbx + (long long)b * io.ld_lbx;
-  const double* ubxb = io.ubx + (long long)b * io.ld_ubx;
-  const double* lbgb = io.lbg + (long long)b * io.ld_lbg;
-  const double* ubgb = io.ubg + (long long)b * io.ld_ubg;
+  const double* yb = R.yb;
   const double* xs = io.x_bar ? io.x_bar + (long long)b * io.ld_x_bar : nullptr;
   const double* ls = io.lam_g_bar ? io.lam_g_bar + (long long)b * io.ld_lam_g_bar : nullptr;
   const double* Xs = io.X_bar ? io.X_bar + (long long)b * io.ld_X_bar : nullptr;
-  S.delta = 0.0;
 
   // every output of the scenario NaN (wave-uniform callers), its verdict and delta out
   auto finish_nan = [&](int verdict, double delta) {
     const long long na = io.na;
-    if (io.pbar)
-      for (long long i = lane; i < na * npE; i += WAVE) io.pbar[(long long)b * na * npE + i] = NAN;
-    if (io.q)
-      for (long long i = lane; i < na * nwE; i += WAVE) io.q[(long long)b * na * nwE + i] = NAN;
-    if (io.jq)
-      for (long long i = lane; i < na * ng; i += WAVE) io.jq[(long long)b * na * ng + i] = NAN;
-    if (lane == 0) {
-      if (io.info) io.info[b] = verdict;
-      if (io.delta) io.delta[b] = delta;
-    }
+    nan_fill(io.pbar ? io.pbar + (long long)b * na * npE : nullptr, na * npE, lane);
+    nan_fill(io.q ? io.q + (long long)b * na * nwE : nullptr, na * nwE, lane);
+    nan_fill(io.jq ? io.jq + (long long)b * na * ng : nullptr, na * ng, lane);
+    point_verdict(S, io.pt, lane, verdict, delta);
   };
 
-  // ---------------- scenario data (as nmpc_kkt_kernel loads it)
-  if (lane < PH_COUNT) S.stamps[lane] = 0.0;
-  for (int i = lane; i < np; i += WAVE) {
-    const int e = ext_p(prm, i);
-    S.pp[i] = e >= 0 ? io.p[(long long)b * io.ld_p + e] : 0.0;
-  }
+  point_load(S, prm, lane, io.pt.p + (long long)b * io.pt.ld_p, R.xb);
   sync();
-  if (lane < NMPC_MAX_OBS) {
-    const bool on = lane < S.nobs;
-    S.obx[lane] = on ? (prm->oxp[lane] >= 0 ? S.pp[prm->oxp[lane]] : prm->ox[lane]) : 0.0;
-    S.oby[lane] = on ? (prm->oyp[lane] >= 0 ? S.pp[prm->oyp[lane]] : prm->oy[lane]) : 0.0;
-  }
-  if (lane == 0) {
-    S.rvars[30] = w1p >= 0 ? S.pp[w1p] : prm->w1;
-    S.rvars[31] = w2p >= 0 ? S.pp[w2p] : prm->w2;
-  }
-  for (int i = lane; i < nw; i += WAVE) {
-    const int e = ext_u(prm, i);
-    S.U[i] = e >= 0 ? xb[e] : 0.0;
-  }
-  for (int r = lane; r < ng; r += WAVE) S.dc[r] = 1.0;  // unscaled rows
-  sync();
-
-  // ---------------- rollout and stage costs (their transcendentals)
-  S.rollout(S.U, S.X);
-  if (lane < N) (void)S.stage_cost(S.X + lane * 8, S.tc + lane * 12);
-  sync();
+  point_rollout(S, lane);
 
   const int k = lane;
   const bool stage = k >= 1 && k <= N;  // the stages whose state depends on w
   const int sv[6] = {0, 1, 2, 5, 6, 7};  // the states a stage cost reads
 
-  // ---------------- the barrier weights: lane k its stage's controls and rows
-  {
-    const double brf = prm->o.bound_relax_factor;
-    bool bad = false;
-    int fmk = 0;
-    if (k < N) {
-#pragma unroll
-      for (int c = 0; c < 6; ++c) {
-        double v = 0.0;
-        if (c < nuE) {
-          const int e = k * nuE + c;
-          const double lo = lbxb[e], hi = ubxb[e];
-          v = lo == hi ? INFINITY : barrier_sigma(xb[e], lxb[e], lo, hi, brf);
-          bad |= lo > hi;
-        }
-        const bool fx = v == INFINITY;
-        bad |= !(v >= 0.0);
-        fmk |= fx ? (1 << c) : 0;
-        Rd[k * 6 + c] = fx ? 0.0 : v;
-        rv[k * 6 + c] = 0.0;
-      }
-    }
-    if (k <= N) {
-      S.fixm[k] = fmk;
-      const LDS double* xk = S.X + k * 8;
-      for (int i = 0; i < m; ++i) {
-        const int r = k * m + i;
-        const double lo = lbgb[r], hi = ubgb[r];
-        const double v = barrier_sigma(gb ? gb[r] : S.row_value(xk, i), yb[r], lo, hi, brf);
-        bad |= lo == hi || !(v >= 0.0) || v == INFINITY;
-        sg[r] = v;
-      }
-    }
-    S.nfix = wany(fmk != 0) ? 1 : 0;
-    if (wany(bad)) {
-      finish_nan(-11, 0.0);
-      return;
-    }
+  if (point_weights(S, prm, R, k)) {
+    finish_nan(-11, 0.0);
+    return;
   }
+  point_derivs(S, R);
 
-  // ---------------- derivatives and multipliers at the scenario's own weights
-  S.derivs<true, true>(S.X, S.U, S.tc);
-  S.adjoint(1.0, yb);
-
-  // second derivatives of lam_{k+1}^T T f(x_k, u_k), stage k < N on lane k (nmpc_kkt_kernel's
-  // expressions): added to the three entries of d2_xx, and S_k's two entries
-  auto dyn2 = [&](double& a33, double& a44, double& a34, double& b03, double& b04) {
-    const LDS double* tg = S.trig + k * 8;
-    const double ct = tg[0], stt = tg[1], cp = tg[2], sp = tg[3], v = tg[4];
-    const LDS double* ln = S.lam + (k + 1) * 8;
-    const double l0 = ln[0], l1 = ln[1], l2 = ln[2];
-    a33 += T * (-l0 * v * cp * ct - l1 * v * sp * ct - l2 * v * stt);
-    a44 += T * (-l0 * v * cp * ct - l1 * v * sp * ct);
-    a34 += T * (l0 * v * sp * stt - l1 * v * cp * stt);
-    b03 = T * (-l0 * cp * stt - l1 * sp * stt + l2 * ct);
-    b04 = T * (-l0 * sp * ct + l1 * cp * ct);
-  };
-
-  // ---------------- lane k: the second-order data of every seed's pullback, in registers
+  // ---------------- lane k: the second-order data of every seed's pullback, in registers.  Not
+  // point_curvature: the curvature of stages k >= 1 alone, only where pbar is wanted, its sum
+  // open to contraction, and the dynamics terms added to zeros as a stage summary adds them
   double q00 = 0.0, q01 = 0.0, q11 = 0.0;
   double d33 = 0.0, d34 = 0.0, d44 = 0.0, s03 = 0.0, s04 = 0.0;  // (stage 0's s03, s04 are not in qs)
   if (io.pbar) {
@@ -244,108 +98,21 @@ __global__ __launch_bounds__(WAVE) void nmpc_solve_adjoint_kernel(const Params* 
         q00 += C * (-ddy * ddy * id3); q01 += C * (ddx * ddy * id3); q11 += C * (-ddx * ddx * id3);
       }
     }
-    if (k < N) dyn2(d33, d44, d34, s03, s04);
-  }
-
-  // ---------------- the delta ladder: stage summaries (nmpc_kkt_kernel's text) and factorisation
-  double delta = 0.0;
-  int verdict = 0;
-  {
-    const double first = prm->o.first_hessian_perturbation, inc_first = prm->o.perturb_inc_fact_first;
-    const double inc = prm->o.perturb_inc_fact, dmax = prm->o.max_hessian_perturbation;
-    while (true) {
-      S.delta = delta;
-      if (k <= N) {
-        double Q[36];
-#pragma unroll
-        for (int t = 0; t < 36; ++t) Q[t] = 0.0;
-        double r03 = 0.0, r04 = 0.0;
-        if (k >= 1) {  // the stages whose state depends on w
-          const LDS double* xk = S.X + k * 8;
-          double Qxy0 = 0, Qxy1 = 0, Qxy2 = 0;
-          double Qb[5] = {0, 0, 0, 0, 0};
-          for (int i = 0; i < m; ++i) {
-            const int r = k * m + i;
-            const double w = sg[r] + delta;
-            if (i < nb) {
-              Qb[i] = w;
-            } else {
-              const double C = yb[r];
-              const int o = i - nb;
-              const double ddx = xk[0] - S.obx[o], ddy = xk[1] - S.oby[o];
-              const double idd = rsq(ddx * ddx + ddy * ddy);
-              const double gx = -(ddx * idd), gy = -(ddy * idd);
-              const double id3 = idd * idd * idd;
-              Qxy0 += w * gx * gx + C * (-ddy * ddy * id3);
-              Qxy1 += w * gx * gy + C * (ddx * ddy * id3);
-              Qxy2 += w * gy * gy + C * (-ddx * ddx * id3);
-            }
-          }
-#pragma unroll
-          for (int a = 0; a < 6; ++a) {
-#pragma unroll
-            for (int bq = a; bq < 6; ++bq) Q[S.pk8(sv[a], sv[bq])] += S.Hl[k * 21 + hp(a, bq)];
-          }
-          Q[S.pk8(0, 0)] += Qxy0; Q[S.pk8(0, 1)] += Qxy1; Q[S.pk8(1, 1)] += Qxy2;
-          Q[S.pk8(2, 2)] += Qb[0]; Q[S.pk8(3, 3)] += Qb[1]; Q[S.pk8(5, 5)] += Qb[2];
-          Q[S.pk8(6, 6)] += Qb[3]; Q[S.pk8(7, 7)] += Qb[4];
-          if (k < N) dyn2(Q[S.pk8(3, 3)], Q[S.pk8(4, 4)], Q[S.pk8(3, 4)], r03, r04);
-        }
-#pragma unroll
-        for (int t = 0; t < 36; ++t) S.Qs[k * 36 + t] = Q[t];
-        LDS double* qo = S.qs + k * 10;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) qo[c] = 0.0;
-        qo[8] = r03;
-        qo[9] = r04;
-      }
-      sync();
-      if (S.riccati(Rd, rv)) break;  // zero linear terms
-      sync();
-      // the next rung, by the host ladder's multiplications
-      const double nxt = delta == 0.0 ? first : (delta == first ? inc_first * delta : inc * delta);
-      if (!(nxt <= dmax) || !(nxt > delta)) {  // (a ladder that does not climb ends here too)
-        verdict = 1;
-        break;
-      }
-      delta = nxt;
+    if (k < N) {
+      const Dyn2 e = point_dyn2(S, k);
+      d33 += T * e.e33; d44 += T * e.e44; d34 += T * e.e34;
+      s03 = T * e.e03; s04 = T * e.e04;
     }
   }
-  if (verdict != 0) {
+
+  double delta;
+  if (const int verdict = point_ladder(S, prm, R, k, 0.0, 0.0, delta)) {
     finish_nan(verdict, delta);
     return;
   }
   sync();
-  if (lane == 0) {
-    if (io.info) io.info[b] = 0;
-    if (io.delta) io.delta[b] = delta;
-  }
-  // ---------------- cost weights from p: unit-weight gradients, lane k stage k's, into the stage
-  // summaries' slice (dead once the factorisation stands; the gradient slice is each seed's)
-  if (io.pbar && (w1p >= 0 || w2p >= 0)) {
-    const double w1s = S.rvars[30], w2s = S.rvars[31];
-    sync();
-    if (w1p >= 0) {
-      if (lane == 0) { S.rvars[30] = 1.0; S.rvars[31] = 0.0; }
-      sync();
-      S.derivs<false, true>(S.X, S.U, S.tc);
-      if (k < N) {
-#pragma unroll
-        for (int a = 0; a < 6; ++a) uw[k * 12 + a] = S.gl[k * 8 + sv[a]];
-      }
-    }
-    if (w2p >= 0) {
-      if (lane == 0) { S.rvars[30] = 0.0; S.rvars[31] = 1.0; }
-      sync();
-      S.derivs<false, true>(S.X, S.U, S.tc);
-      if (k < N) {
-#pragma unroll
-        for (int a = 0; a < 6; ++a) uw[k * 12 + 6 + a] = S.gl[k * 8 + sv[a]];
-      }
-    }
-    if (lane == 0) { S.rvars[30] = w1s; S.rvars[31] = w2s; }
-    sync();
-  }
+  point_verdict(S, io.pt, lane, 0, delta);
+  if (io.pbar) point_unit_grads(S, prm, R, lane);
 
   // the internal entry of p this lane forms, and its place in the caller's layout
   const int pe = lane < np ? ext_p(prm, lane) : -1;

@@ -957,6 +957,110 @@ class Solver:
         pbar[:, :, r["info"] != 0] = np.nan
         return {"pbar": pbar, "info": r["info"], "delta": delta, "q": r["dw"], "jq": r["jdw"]}
 
+    # ---- what the three entry points at a solve's point marshal alike (nmpc_solve_adjoint_batch,
+    # nmpc_solve_tangent_batch, nmpc_solve_policy_batch and their _dev twins)
+    def _point_fields(self, sol, lbx, ubx, lbg, ubg, p):
+        """The nine point inputs in the C argument order: (name, value, length)."""
+        return (("x", sol["x"], self.nw), ("p", p, self.np), ("lam_g", sol["lam_g"], self.ng),
+                ("lam_x", sol["lam_x"], self.nw), ("g", sol.get("g"), self.ng), ("lbx", lbx, self.nw),
+                ("ubx", ubx, self.nw), ("lbg", lbg, self.ng), ("ubg", ubg, self.ng))
+
+    def _point_ins_host(self, sol, lbx, ubx, lbg, ubg, p):
+        """NumPy: the nine point inputs as ``[(array, ld)]`` (an absent one ``(None, 0)``), and B."""
+        x, ld_x = self._arg(sol["x"], self.nw, 0.0, "x")
+        B = x.shape[0]
+        ins = [(x, ld_x)]
+        for name, a, n in self._point_fields(sol, lbx, ubx, lbg, ubg, p)[1:]:
+            if a is None:
+                ins.append((None, 0))
+                continue
+            a, ld = self._arg(a, n, 0.0, name)
+            if ld and a.shape[0] != B:
+                raise ValueError(f"{name}: batch size {a.shape[0]} does not match {B}")
+            ins.append((a, ld))
+        return ins, B
+
+    @staticmethod
+    def _flat_ins(ins):
+        flat = []
+        for a, ld in ins:
+            flat += [_dptr(a) if a is not None else None, ld]
+        return flat
+
+    def _point_ins_device(self, sol, lbx, ubx, lbg, ubg, p, B=None):
+        """torch: the nine point inputs as a flat ``[pointer, ld, ...]``, and B (the outputs'
+        when given, else x's)."""
+        import torch  # plumbing only: device memory and streams
+
+        for k in ("x", "lam_g", "lam_x"):
+            if sol.get(k) is None:
+                raise ValueError(f"sol: {k} is required")
+        if B is None:
+            B = sol["x"].shape[0]
+
+        def dv(t, n, name):
+            if t is None:
+                return C.c_void_p(0), 0
+            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), name
+            if t.dim() == 1:
+                assert t.shape[0] == n, name
+                return C.c_void_p(t.data_ptr()), 0
+            assert t.shape == (B, n), (name, tuple(t.shape), (B, n))
+            return C.c_void_p(t.data_ptr()), n
+
+        ins = []
+        for name, t, n in self._point_fields(sol, lbx, ubx, lbg, ubg, p):
+            if t is None and name != "g":
+                raise ValueError(f"{name} is required")
+            ins += list(dv(t, n, name))
+        return ins, B
+
+    def _dp_dirs(self, dp, nd_min):
+        """``dp`` (np,), (np,nd) or (np,nd,B) as a float64 array of 2 or 3 dimensions, and nd."""
+        d = np.asarray(dp, dtype=np.float64)
+        if d.ndim == 1:
+            d = d.reshape(-1, 1)
+        if d.ndim not in (2, 3) or d.shape[0] != self.np or d.shape[1] < nd_min:
+            raise ValueError(f"dp: expected ({self.np},), ({self.np},nd) or ({self.np},nd,B), got shape {d.shape}")
+        return d, d.shape[1]
+
+    def _dp_arg(self, d, B):
+        """:meth:`_dp_dirs`' array in the C layout with its leading dimension."""
+        if d.ndim == 3:
+            if d.shape[2] != B:
+                raise ValueError(f"dp: batch size {d.shape[2]} does not match {B}")
+            return np.ascontiguousarray(d.transpose(2, 1, 0)), self.np * d.shape[1]  # (B, nd, np)
+        return np.ascontiguousarray(d.T), 0  # (nd, np), shared
+
+    def _dp_device(self, dp, nd, B):
+        import torch  # plumbing only
+
+        assert dp.dtype == torch.float64 and dp.is_cuda and dp.is_contiguous(), "dp"
+        assert tuple(dp.shape) in ((nd, self.np), (B, nd, self.np)), ("dp", tuple(dp.shape))
+        return [C.c_void_p(dp.data_ptr()), 0 if dp.dim() == 2 else nd * self.np]
+
+    @staticmethod
+    def _out_ptrs_device(out, shapes):
+        """Pointers of the given device outputs (null where absent), each checked against its
+        shape; info is int32, every other float64."""
+        import torch  # plumbing only
+
+        ptrs = []
+        for k, shp in shapes:
+            t = out.get(k)
+            if t is not None:
+                dt = torch.int32 if k == "info" else torch.float64
+                assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp, k
+            ptrs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
+        return ptrs
+
+    def _raise_equality_rows(self, info, lbg, ubg, caller):
+        """info = -11 with an equality row: the ``ValueError`` of :meth:`barrier_weights`."""
+        if np.any(info == -11):
+            lo, hi = (np.asarray(v, dtype=np.float64).reshape(self.ng, -1) for v in (lbg, ubg))
+            if np.any(lo == hi):
+                raise ValueError(f"{caller}: equality rows (lbg == ubg) are not supported")
+
     # ---- the same in one launch (nmpc_solve_adjoint_batch: weights, ladder, solves, pullback)
     def sensitivity_adjoint_fused(self, sol: dict, lbx, ubx, lbg, ubg, p, x_bar=None, lam_g_bar=None, X_bar=None):
         """:meth:`sensitivity_adjoint` as one kernel launch: the same arguments, the same dict
@@ -965,19 +1069,7 @@ class Solver:
         otherwise), the delta ladder, the solves and the pullback all run on the device; the
         host only stages the arrays.  Equality rows raise ``ValueError``, as
         :meth:`barrier_weights` does."""
-        x, ld_x = self._arg(sol["x"], self.nw, 0.0, "x")
-        B = x.shape[0]
-        ins = [(x, ld_x)]
-        for name, a, n in (("p", p, self.np), ("lam_g", sol["lam_g"], self.ng), ("lam_x", sol["lam_x"], self.nw),
-                           ("g", sol.get("g"), self.ng), ("lbx", lbx, self.nw), ("ubx", ubx, self.nw),
-                           ("lbg", lbg, self.ng), ("ubg", ubg, self.ng)):
-            if a is None:
-                ins.append((None, 0))
-                continue
-            a, ld = self._arg(a, n, 0.0, name)
-            if ld and a.shape[0] != B:
-                raise ValueError(f"{name}: batch size {a.shape[0]} does not match {B}")
-            ins.append((a, ld))
+        ins, B = self._point_ins_host(sol, lbx, ubx, lbg, ubg, p)
         na = None
         for name, r, n in (("x_bar", x_bar, self.nw), ("lam_g_bar", lam_g_bar, self.ng), ("X_bar", X_bar, self.nX)):
             if r is None:
@@ -994,16 +1086,10 @@ class Solver:
             raise ValueError("x_bar, lam_g_bar or X_bar is required")
         out = {"pbar": np.empty((B, na, self.np)), "q": np.empty((B, na, self.nw)), "jq": np.empty((B, na, self.ng))}
         info, delta = np.empty(B, dtype=np.int32), np.empty(B)
-        flat = []
-        for a, ld in ins:
-            flat += [_dptr(a) if a is not None else None, ld]
         _lib.check(_lib.lib().nmpc_solve_adjoint_batch(
-            self._h, B, na, *flat, _dptr(out["pbar"]), _dptr(out["q"]), _dptr(out["jq"]),
+            self._h, B, na, *self._flat_ins(ins), _dptr(out["pbar"]), _dptr(out["q"]), _dptr(out["jq"]),
             info.ctypes.data_as(_IP), _dptr(delta)))
-        if np.any(info == -11):
-            lo, hi = (np.asarray(v, dtype=np.float64).reshape(self.ng, -1) for v in (lbg, ubg))
-            if np.any(lo == hi):
-                raise ValueError("sensitivity_adjoint_fused: equality rows (lbg == ubg) are not supported")
+        self._raise_equality_rows(info, lbg, ubg, "sensitivity_adjoint_fused")
         res = {k: np.ascontiguousarray(t.transpose(2, 1, 0)) for k, t in out.items()}
         res["info"], res["delta"] = info, delta
         return res
@@ -1028,16 +1114,6 @@ class Solver:
             raise ValueError("x_bar, lam_g_bar or X_bar is required")
         B, na = given[0].shape[0], given[0].shape[1]
 
-        def dv(t, n, name):
-            if t is None:
-                return C.c_void_p(0), 0
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), name
-            if t.dim() == 1:
-                assert t.shape[0] == n, name
-                return C.c_void_p(t.data_ptr()), 0
-            assert t.shape == (B, n), (name, tuple(t.shape), (B, n))
-            return C.c_void_p(t.data_ptr()), n
-
         def sv(t, n, name):
             if t is None:
                 return C.c_void_p(0), 0
@@ -1045,29 +1121,11 @@ class Solver:
             assert tuple(t.shape) in ((na, n), (B, na, n)), (name, tuple(t.shape))
             return C.c_void_p(t.data_ptr()), (0 if t.dim() == 2 else na * n)
 
-        for k in ("x", "lam_g", "lam_x"):
-            if sol.get(k) is None:
-                raise ValueError(f"sol: {k} is required")
-        ins = []
-        for name, t, n in (("x", sol["x"], self.nw), ("p", p, self.np), ("lam_g", sol["lam_g"], self.ng),
-                           ("lam_x", sol["lam_x"], self.nw), ("g", sol.get("g"), self.ng), ("lbx", lbx, self.nw),
-                           ("ubx", ubx, self.nw), ("lbg", lbg, self.ng), ("ubg", ubg, self.ng)):
-            if t is None and name != "g":
-                raise ValueError(f"{name} is required")
-            ins += list(dv(t, n, name))
+        ins, _ = self._point_ins_device(sol, lbx, ubx, lbg, ubg, p, B)
         ins += (list(sv(x_bar, self.nw, "x_bar")) + list(sv(lam_g_bar, self.ng, "lam_g_bar"))
                 + list(sv(X_bar, self.nX, "X_bar")))
-        outs = []
-        for k, n in (("pbar", self.np), ("q", self.nw), ("jq", self.ng)):
-            t = out.get(k)
-            if t is not None:
-                assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B, na, n), k
-            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
-        for k, dt in (("info", torch.int32), ("delta", torch.float64)):
-            t = out.get(k)
-            if t is not None:
-                assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B,), k
-            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
+        outs = self._out_ptrs_device(out, (("pbar", (B, na, self.np)), ("q", (B, na, self.nw)),
+                                           ("jq", (B, na, self.ng)), ("info", (B,)), ("delta", (B,))))
         if stream is None:
             stream = torch.cuda.current_stream()
         _lib.check(_lib.lib().nmpc_solve_adjoint_batch_dev(self._h, B, na, *ins, *outs,
@@ -1084,43 +1142,15 @@ class Solver:
         ladder and the solves all run on the device; the host only stages the arrays.  A scenario
         whose ``info`` is not 0 has NaN in dx, dlam_g and dX.  Equality rows raise
         ``ValueError``, as :meth:`barrier_weights` does."""
-        d = np.asarray(dp, dtype=np.float64)
-        if d.ndim == 1:
-            d = d.reshape(-1, 1)
-        if d.ndim not in (2, 3) or d.shape[0] != self.np or d.shape[1] < 1:
-            raise ValueError(f"dp: expected ({self.np},), ({self.np},nd) or ({self.np},nd,B), got shape {d.shape}")
-        nd = d.shape[1]
-        x, ld_x = self._arg(sol["x"], self.nw, 0.0, "x")
-        B = x.shape[0]
-        ins = [(x, ld_x)]
-        for name, a, n in (("p", p, self.np), ("lam_g", sol["lam_g"], self.ng), ("lam_x", sol["lam_x"], self.nw),
-                           ("g", sol.get("g"), self.ng), ("lbx", lbx, self.nw), ("ubx", ubx, self.nw),
-                           ("lbg", lbg, self.ng), ("ubg", ubg, self.ng)):
-            if a is None:
-                ins.append((None, 0))
-                continue
-            a, ld = self._arg(a, n, 0.0, name)
-            if ld and a.shape[0] != B:
-                raise ValueError(f"{name}: batch size {a.shape[0]} does not match {B}")
-            ins.append((a, ld))
-        if d.ndim == 3:
-            if d.shape[2] != B:
-                raise ValueError(f"dp: batch size {d.shape[2]} does not match {B}")
-            ins.append((np.ascontiguousarray(d.transpose(2, 1, 0)), self.np * nd))  # (B, nd, np)
-        else:
-            ins.append((np.ascontiguousarray(d.T), 0))  # (nd, np), shared
+        d, nd = self._dp_dirs(dp, 1)
+        ins, B = self._point_ins_host(sol, lbx, ubx, lbg, ubg, p)
+        ins.append(self._dp_arg(d, B))
         out = {"dx": np.empty((B, nd, self.nw)), "dlam_g": np.empty((B, nd, self.ng)), "dX": np.empty((B, nd, self.nX))}
         info, delta = np.empty(B, dtype=np.int32), np.empty(B)
-        flat = []
-        for a, ld in ins:
-            flat += [_dptr(a) if a is not None else None, ld]
         _lib.check(_lib.lib().nmpc_solve_tangent_batch(
-            self._h, B, nd, *flat, _dptr(out["dx"]), _dptr(out["dlam_g"]), _dptr(out["dX"]),
+            self._h, B, nd, *self._flat_ins(ins), _dptr(out["dx"]), _dptr(out["dlam_g"]), _dptr(out["dX"]),
             info.ctypes.data_as(_IP), _dptr(delta)))
-        if np.any(info == -11):
-            lo, hi = (np.asarray(v, dtype=np.float64).reshape(self.ng, -1) for v in (lbg, ubg))
-            if np.any(lo == hi):
-                raise ValueError("sensitivity_fused: equality rows (lbg == ubg) are not supported")
+        self._raise_equality_rows(info, lbg, ubg, "sensitivity_fused")
         res = {k: np.ascontiguousarray(t.transpose(2, 1, 0)) for k, t in out.items()}
         res["info"], res["delta"] = info, delta
         return res
@@ -1142,41 +1172,10 @@ class Solver:
         if dp is None:
             raise ValueError("dp is required")
         B, nd = given[0].shape[0], given[0].shape[1]
-
-        def dv(t, n, name):
-            if t is None:
-                return C.c_void_p(0), 0
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), name
-            if t.dim() == 1:
-                assert t.shape[0] == n, name
-                return C.c_void_p(t.data_ptr()), 0
-            assert t.shape == (B, n), (name, tuple(t.shape), (B, n))
-            return C.c_void_p(t.data_ptr()), n
-
-        for k in ("x", "lam_g", "lam_x"):
-            if sol.get(k) is None:
-                raise ValueError(f"sol: {k} is required")
-        ins = []
-        for name, t, n in (("x", sol["x"], self.nw), ("p", p, self.np), ("lam_g", sol["lam_g"], self.ng),
-                           ("lam_x", sol["lam_x"], self.nw), ("g", sol.get("g"), self.ng), ("lbx", lbx, self.nw),
-                           ("ubx", ubx, self.nw), ("lbg", lbg, self.ng), ("ubg", ubg, self.ng)):
-            if t is None and name != "g":
-                raise ValueError(f"{name} is required")
-            ins += list(dv(t, n, name))
-        assert dp.dtype == torch.float64 and dp.is_cuda and dp.is_contiguous(), "dp"
-        assert tuple(dp.shape) in ((nd, self.np), (B, nd, self.np)), ("dp", tuple(dp.shape))
-        ins += [C.c_void_p(dp.data_ptr()), 0 if dp.dim() == 2 else nd * self.np]
-        outs = []
-        for k, n in (("dx", self.nw), ("dlam_g", self.ng), ("dX", self.nX)):
-            t = out.get(k)
-            if t is not None:
-                assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B, nd, n), k
-            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
-        for k, dt in (("info", torch.int32), ("delta", torch.float64)):
-            t = out.get(k)
-            if t is not None:
-                assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B,), k
-            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
+        ins, _ = self._point_ins_device(sol, lbx, ubx, lbg, ubg, p, B)
+        ins += self._dp_device(dp, nd, B)
+        outs = self._out_ptrs_device(out, (("dx", (B, nd, self.nw)), ("dlam_g", (B, nd, self.ng)),
+                                           ("dX", (B, nd, self.nX)), ("info", (B,)), ("delta", (B,))))
         if stream is None:
             stream = torch.cuda.current_stream()
         _lib.check(_lib.lib().nmpc_solve_tangent_batch_dev(self._h, B, nd, *ins, *outs,
@@ -1225,52 +1224,19 @@ class Solver:
         scenario whose ``info`` is not 0 has NaN in every array.  Equality rows raise
         ``ValueError``, as :meth:`sensitivity_fused` does."""
         N, nu, nx = self._policy_dims()
-        d = None
-        nd = 0
-        if dp is not None:
-            d = np.asarray(dp, dtype=np.float64)
-            if d.ndim == 1:
-                d = d.reshape(-1, 1)
-            if d.ndim not in (2, 3) or d.shape[0] != self.np:
-                raise ValueError(f"dp: expected ({self.np},), ({self.np},nd) or ({self.np},nd,B), got shape {d.shape}")
-            nd = d.shape[1]
-            if nd == 0:
-                d = None
-        x, ld_x = self._arg(sol["x"], self.nw, 0.0, "x")
-        B = x.shape[0]
-        ins = [(x, ld_x)]
-        for name, a, n in (("p", p, self.np), ("lam_g", sol["lam_g"], self.ng), ("lam_x", sol["lam_x"], self.nw),
-                           ("g", sol.get("g"), self.ng), ("lbx", lbx, self.nw), ("ubx", ubx, self.nw),
-                           ("lbg", lbg, self.ng), ("ubg", ubg, self.ng)):
-            if a is None:
-                ins.append((None, 0))
-                continue
-            a, ld = self._arg(a, n, 0.0, name)
-            if ld and a.shape[0] != B:
-                raise ValueError(f"{name}: batch size {a.shape[0]} does not match {B}")
-            ins.append((a, ld))
-        if d is None:
-            ins.append((None, 0))
-        elif d.ndim == 3:
-            if d.shape[2] != B:
-                raise ValueError(f"dp: batch size {d.shape[2]} does not match {B}")
-            ins.append((np.ascontiguousarray(d.transpose(2, 1, 0)), self.np * nd))  # (B, nd, np)
-        else:
-            ins.append((np.ascontiguousarray(d.T), 0))  # (nd, np), shared
+        d, nd = (None, 0) if dp is None else self._dp_dirs(dp, 0)
+        if nd == 0:
+            d = None
+        ins, B = self._point_ins_host(sol, lbx, ubx, lbg, ubg, p)
+        ins.append((None, 0) if d is None else self._dp_arg(d, B))
         K, A, Bm = np.empty((B, N, nx, nu)), np.empty((B, N, nx, nx)), np.empty((B, N, nu, nx))
         kff = np.empty((B, nd, N, nu)) if nd else None
         X = np.empty((B, N + 1, nx))
         info, delta = np.empty(B, dtype=np.int32), np.empty(B)
-        flat = []
-        for a, ld in ins:
-            flat += [_dptr(a) if a is not None else None, ld]
         _lib.check(_lib.lib().nmpc_solve_policy_batch(
-            self._h, B, nd, *flat, _dptr(K), _dptr(kff) if nd else None, _dptr(A), _dptr(Bm), _dptr(X),
-            info.ctypes.data_as(_IP), _dptr(delta)))
-        if np.any(info == -11):
-            lo, hi = (np.asarray(v, dtype=np.float64).reshape(self.ng, -1) for v in (lbg, ubg))
-            if np.any(lo == hi):
-                raise ValueError("policy_fused: equality rows (lbg == ubg) are not supported")
+            self._h, B, nd, *self._flat_ins(ins), _dptr(K), _dptr(kff) if nd else None, _dptr(A), _dptr(Bm),
+            _dptr(X), info.ctypes.data_as(_IP), _dptr(delta)))
+        self._raise_equality_rows(info, lbg, ubg, "policy_fused")
         # the blocks are column-major: K_k is stored (nx, nu), A_k (nx, nx), B_k (nu, nx)
         return {"K": np.ascontiguousarray(K.transpose(0, 1, 3, 2)), "kff": kff,
                 "A": np.ascontiguousarray(A.transpose(0, 1, 3, 2)), "B": np.ascontiguousarray(Bm.transpose(0, 1, 3, 2)),
@@ -1290,38 +1256,10 @@ class Solver:
         import torch  # plumbing only: device memory and streams
 
         N, nu, nx = self._policy_dims()
-        for k in ("x", "lam_g", "lam_x"):
-            if sol.get(k) is None:
-                raise ValueError(f"sol: {k} is required")
+        ins, B = self._point_ins_device(sol, lbx, ubx, lbg, ubg, p)
         x = sol["x"]
-        B = x.shape[0]
         nd = 0 if dp is None else dp.shape[-2]
-        if nd == 0:
-            dp = None
-
-        def dv(t, n, name):
-            if t is None:
-                return C.c_void_p(0), 0
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), name
-            if t.dim() == 1:
-                assert t.shape[0] == n, name
-                return C.c_void_p(t.data_ptr()), 0
-            assert t.shape == (B, n), (name, tuple(t.shape), (B, n))
-            return C.c_void_p(t.data_ptr()), n
-
-        ins = []
-        for name, t, n in (("x", x, self.nw), ("p", p, self.np), ("lam_g", sol["lam_g"], self.ng),
-                           ("lam_x", sol["lam_x"], self.nw), ("g", sol.get("g"), self.ng), ("lbx", lbx, self.nw),
-                           ("ubx", ubx, self.nw), ("lbg", lbg, self.ng), ("ubg", ubg, self.ng)):
-            if t is None and name != "g":
-                raise ValueError(f"{name} is required")
-            ins += list(dv(t, n, name))
-        if dp is not None:
-            assert dp.dtype == torch.float64 and dp.is_cuda and dp.is_contiguous(), "dp"
-            assert tuple(dp.shape) in ((nd, self.np), (B, nd, self.np)), ("dp", tuple(dp.shape))
-            ins += [C.c_void_p(dp.data_ptr()), 0 if dp.dim() == 2 else nd * self.np]
-        else:
-            ins += [C.c_void_p(0), 0]
+        ins += self._dp_device(dp, nd, B) if nd else [C.c_void_p(0), 0]
         if stream is None:
             stream = torch.cuda.current_stream()
         shapes = {"K": (B, N, nx, nu), "kff": (B, nd, N, nu), "A": (B, N, nx, nx), "B": (B, N, nu, nx),

@@ -5,6 +5,13 @@
     python scripts/ab_bitwise.py out_a.npz        # default library
     NMPC_LIB=exp/other.so python scripts/ab_bitwise.py out_b.npz
     python scripts/ab_bitwise.py --compare out_a.npz out_b.npz
+
+With --fused before the file name the dump is every output of the three entry points at a solve's
+point (sensitivity_adjoint_fused, sensitivity_fused, policy_fused) and of kkt_solve instead: on
+the solved cases of tests/solve_adjoint_ref.py (na = 3 seeds of all three kinds, nd = 3
+directions), and on one batch per exit of the kernels -- fixed controls, info = -11, and info = 1
+with the ladder exhausted.  The points themselves are dumped too, so equal inputs are shown, and
+--compare takes NaNs in the same places as equal whatever their payloads.
 """
 import os, sys
 import numpy as np
@@ -18,15 +25,87 @@ def compare(a, b):
     for k in A.files:
         x, y = A[k], Bz[k]
         same = x.shape == y.shape and np.ascontiguousarray(x).tobytes() == np.ascontiguousarray(y).tobytes()
+        if not same and x.shape == y.shape and x.dtype.kind == "f":  # NaN payloads may differ, positions not
+            nx = np.isnan(x)
+            same = np.array_equal(nx, np.isnan(y)) and (
+                np.where(nx, 0.0, x).tobytes() == np.where(nx, 0.0, y).tobytes())
         ndiff = int(np.sum(x != y)) if not same else 0
-        print(f"{k:14s} {'bitwise equal' if same else f'DIFFERS in {ndiff} entries'}")
+        print(f"{k:28s} {'bitwise equal' if same else f'DIFFERS in {ndiff} entries'}")
         bad += not same
     return bad
+
+
+def fused(path):
+    sys.path.insert(0, ROOT)
+    from nmpc_amd import nlpsol, REFERENCE_OPTS
+    from tests import solve_adjoint_ref as sr
+
+    def solver(spec, **ipopt):
+        return nlpsol("solver", "ipopt", spec, dict(REFERENCE_OPTS, ipopt=dict(REFERENCE_OPTS["ipopt"], **ipopt)))
+
+    out = {}
+
+    def dump(tag, s, sol, bounds, P, B, spec, seed):
+        rng = np.random.default_rng(seed)
+        sd = {k: rng.standard_normal((n, 3, B)) for k, n in (("x_bar", spec.nw), ("lam_g_bar", spec.ng),
+                                                              ("X_bar", spec.nX))}
+        dp = rng.standard_normal((spec.np, 3, B))
+        for name, r in (("adj", s.sensitivity_adjoint_fused(sol, *bounds, P.T, **sd)),
+                        ("tan", s.sensitivity_fused(sol, *bounds, P.T, dp)),
+                        ("pol", s.policy_fused(sol, *bounds, P.T, dp))):
+            for k, v in r.items():
+                out[f"{tag}_{name}_{k}"] = np.asarray(v)
+        print(tag, "info", out[f"{tag}_adj_info"], out[f"{tag}_tan_info"], out[f"{tag}_pol_info"], "delta",
+              out[f"{tag}_tan_delta"])
+        return sd
+
+    for name, (B, _) in sr.SOLVED.items():
+        spec, P = sr.scenarios(name)
+        s = solver(spec)
+        bounds = spec.bounds()
+        sol = s(x0=np.zeros(spec.nw), lbx=bounds[0], ubx=bounds[1], lbg=bounds[2], ubg=bounds[3], p=P.T)
+        sol = {k: np.array(sol[k], dtype=np.float64).reshape(-1, B) for k in ("x", "g", "lam_x", "lam_g")}
+        for k, v in sol.items():
+            out[f"{name}_point_{k}"] = v
+        sd = dump(name, s, sol, bounds, P, B, spec, 1)
+        # the KKT solves at the point's weights, at delta = 0 and at a delta every case factorises with
+        sx, ss = s.barrier_weights(sol, *bounds)
+        for dl in (0.0, 1e-4):
+            r = s.kkt_solve(sol["x"], P.T, r_w=sd["x_bar"], r_g=sd["lam_g_bar"], lam_g=sol["lam_g"], sigma_x=sx,
+                            sigma_s=ss, delta=dl)
+            for k, v in r.items():
+                out[f"{name}_kkt{dl:g}_{k}"] = np.asarray(v)
+        if name != "race_track_2":
+            continue
+        lbx, ubx, lbg, ubg = bounds
+        nu = spec.nw // spec.N
+        # a third of the controls fixed, a whole stage among them
+        fx = np.random.default_rng(78).uniform(size=(spec.nw, B)) < 1.0 / 3.0
+        fx[:nu, 0] = True
+        lb2, ub2 = (np.repeat(v[:, None], B, axis=1) for v in (lbx, ubx))
+        lb2[fx], ub2[fx] = sol["x"][fx], sol["x"][fx]
+        dump("fixed", s, sol, (lb2, ub2, lbg, ubg), P, B, spec, 2)
+        # info = -11: lbx > ubx in scenario 1, a NaN multiplier in scenario 2
+        lb3, ub3 = (np.repeat(v[:, None], B, axis=1) for v in (lbx, ubx))
+        lb3[5, 1] = ub3[5, 1] + 1.0
+        sol3 = dict(sol, lam_g=sol["lam_g"].copy())
+        sol3["lam_g"][3, 2] = np.nan
+        dump("invalid", s, sol3, (lb3, ub3, lbg, ubg), P, B, spec, 3)
+        # the ladder: many rungs from 1e-12, then none allowed (info = 1) but for scenario 0, whose last
+        # stage is fixed
+        dump("rungs", solver(spec, first_hessian_perturbation=1e-12), sol, bounds, P, B, spec, 4)
+        lb4, ub4 = (np.repeat(v[:, None], B, axis=1) for v in (lbx, ubx))
+        lb4[-nu:, 0] = ub4[-nu:, 0] = sol["x"][-nu:, 0]
+        dump("stuck", solver(spec, max_hessian_perturbation=1e-6), sol, (lb4, ub4, lbg, ubg), P, B, spec, 5)
+    np.savez(path, **{k: v for k, v in out.items() if v.dtype != object})
+    print("saved", path, len(out), "arrays")
 
 
 def main():
     if sys.argv[1] == "--compare":
         sys.exit(1 if compare(sys.argv[2], sys.argv[3]) else 0)
+    if sys.argv[1] == "--fused":
+        return fused(sys.argv[2])
     import torch
     from nmpc_amd import nlpsol, config_spec, draw_scenarios, REFERENCE_OPTS
     B = int(os.environ.get("AB_B", "4096")); K = int(os.environ.get("AB_K", "20"))

@@ -48,8 +48,8 @@ def test_invalid_arguments_are_refused_before_any_device_call():
 
 def test_policy_kernel_lives_in_the_evaluation_unit(tmp_path, monkeypatch):
     """Still nine translation units: the kernel's file is included by nmpc_eval.hip after
-    nmpc_solve_tangent.hip, whose LDS carve-up and workspace slices it uses, and the library's
-    build id covers it."""
+    nmpc_solve_tangent.hip (both on nmpc_point.hip's LDS carve-up and workspace slices), and the
+    library's build id covers it."""
     assert len(ge._TUS) == 9 and ge._TUS[-1] == ("eval", "nmpc_eval.hip")
     with open(os.path.join(ge.CSRC, "nmpc_eval.hip")) as fh:
         text = fh.read()

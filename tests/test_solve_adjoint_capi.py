@@ -49,12 +49,14 @@ def test_null_handle_is_invalid_for_both_entry_points():
 
 def test_fused_kernel_lives_in_the_evaluation_unit(tmp_path, monkeypatch):
     """Still nine translation units: the kernel's file is included by nmpc_eval.hip after
-    nmpc_adjoint.hip, and the library's build id covers it."""
+    nmpc_adjoint.hip and after nmpc_point.hip, the steps it shares with the tangent and policy
+    kernels, and the library's build id covers both files."""
     assert len(ge._TUS) == 9 and ge._TUS[-1] == ("eval", "nmpc_eval.hip")
     with open(os.path.join(ge.CSRC, "nmpc_eval.hip")) as fh:
         text = fh.read()
-    assert '#include "nmpc_solve_adjoint.hip"' in text
-    assert text.index('#include "nmpc_adjoint.hip"') < text.index('#include "nmpc_solve_adjoint.hip"')
+    assert '#include "nmpc_solve_adjoint.hip"' in text and '#include "nmpc_point.hip"' in text
+    assert (text.index('#include "nmpc_adjoint.hip"') < text.index('#include "nmpc_point.hip"')
+            < text.index('#include "nmpc_solve_adjoint.hip"'))
     copy = tmp_path / "csrc"
     shutil.copytree(ge.CSRC, copy)
     before = ge.source_hash()
@@ -62,7 +64,11 @@ def test_fused_kernel_lives_in_the_evaluation_unit(tmp_path, monkeypatch):
     assert ge.source_hash() == before
     with open(copy / "nmpc_solve_adjoint.hip", "ab") as fh:
         fh.write(b"\n// x\n")
-    assert ge.source_hash() != before
+    moved = ge.source_hash()
+    assert moved != before
+    with open(copy / "nmpc_point.hip", "ab") as fh:
+        fh.write(b"x")
+    assert ge.source_hash() not in (before, moved)
 
 
 STEP = 1e-3
