@@ -591,6 +591,63 @@ int nmpc_solve_policy_batch(nmpc_handle* h, int32_t B, int32_t nd,
                             double* K_out, double* kff_out, double* A_out, double* B_out, double* X_out,
                             int32_t* info_out, double* delta_out);
 
+/* Disturbance rollouts of that policy on the nonlinear plant, for a whole batch, in one launch:
+ * what the clamped policy costs and whether it keeps the rows when the state drifts.  For each of B
+ * scenarios and each of M samples s, in fp64 and in the model's own dimensions (the no-gimbal model:
+ * nu = 3, nx = 5):
+ *   x_0 = p[x0 block] + e0[s]
+ *   for k = 0 ... N-1:
+ *     u_raw = ubar_k + K_k (x_k - Xbar_k)          (K NULL: u_raw = ubar_k, open-loop replay)
+ *     u_k   = min(max(u_raw, lbx_k), ubx_k)        (lbx / ubx NULL: that side is not clamped)
+ *     J    += stage_cost(x_k; p)                   (summed in stage order)
+ *     x_{k+1} = x_k + T f(x_k, u_k) + w_k[s]       (w NULL: no process disturbance)
+ *   viol = max over all ng rows r of max(g_r - ubg_r, lbg_r - g_r, 0)
+ *          (rows of stages 0 ... N at x_0 ... x_N, g_out's row order; the +-1e19 rule; lbg and
+ *          ubg NULL: no row has a bound, viol = 0)
+ *   nsat = number of control entries u_k differs from u_raw in
+ * The kernel knows nothing about directions: ubar is caller-formed (for a parameter move
+ * u* + sum_d kff^(d) c_d, and p the moved parameter vector).  K, Xbar and ubar have the layouts
+ * nmpc_solve_policy_batch_dev's K_out and X_out and the solve's x_out have, so those buffers can be
+ * passed straight in.  The plant's operations are those of the solve's own rollout in the same
+ * order: a sample with e0 = 0, no w and no active clamp reproduces X_out of nmpc_eval_batch_dev.
+ * Inputs (leading dimension: 0 shares one column across scenarios, else >= the vector length):
+ *   p    (np x B)        required        ubar (nw x B)         required
+ *   Xbar (nx(N+1) x B)   required        K    (nu nx N x B)    optional
+ *   lbx, ubx (nw x B)    optional, each  lbg, ubg (ng x B)     optional, both or neither
+ *   e0   (nx M x B)      required: sample s occupies [s nx, (s+1) nx)
+ *   w    (nx N M x B)    optional: sample s, stage k occupy [(s N + k) nx, (s N + k + 1) nx)
+ * Outputs, each may be NULL, at least one of J_out, viol_out, X_out, U_out must be given:
+ *   J_out, viol_out (M x B), nsat_out (M x B, int32): sample s of scenario b at b M + s
+ *   X_out (nx(N+1) x M x B): x_0 ... x_N of sample s of scenario b from (b M + s) nx (N+1)
+ *   U_out (nw x M x B)      : u_0 ... u_{N-1} likewise
+ * A NaN among a sample's states, controls, row values or the bounds it meets gives NaN in that
+ * sample's J and viol only (the row maximum does not drop it); a scenario whose policy is NaN
+ * (info != 0) therefore yields NaN samples beside untouched neighbours.  States that leave the
+ * cost's domain are reported as they come (inf / NaN), not trapped.
+ * DEVICE pointers, enqueued on `stream`; never synchronises, allocates nothing and needs no
+ * workspace (each sample's state lives in on-chip memory): the handle's memory is untouched.
+ * A NULL handle, B <= 0, M <= 0 (or M > 64 x 65535), a NULL p, ubar, Xbar or e0, J_out, viol_out,
+ * X_out and U_out all NULL, lbg without ubg or the reverse, or a leading dimension that is neither
+ * 0 nor >= the vector length return NMPC_E_INVALID before any device call. */
+int nmpc_policy_rollout_batch_dev(nmpc_handle* h, int32_t B, int32_t M,
+                                  const double* p, int64_t ld_p, const double* ubar, int64_t ld_ubar,
+                                  const double* Xbar, int64_t ld_Xbar, const double* K, int64_t ld_K,
+                                  const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx,
+                                  const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg,
+                                  const double* e0, int64_t ld_e0, const double* w, int64_t ld_w,
+                                  double* J_out, double* viol_out, int32_t* nsat_out, double* X_out,
+                                  double* U_out, void* stream);
+
+/* Same with HOST pointers; synchronous (staged through the handle's device buffer). */
+int nmpc_policy_rollout_batch(nmpc_handle* h, int32_t B, int32_t M,
+                              const double* p, int64_t ld_p, const double* ubar, int64_t ld_ubar,
+                              const double* Xbar, int64_t ld_Xbar, const double* K, int64_t ld_K,
+                              const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx,
+                              const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg,
+                              const double* e0, int64_t ld_e0, const double* w, int64_t ld_w,
+                              double* J_out, double* viol_out, int32_t* nsat_out, double* X_out,
+                              double* U_out);
+
 /* Optional per-iteration trace (debugging / parity): when enabled, the next
  * solve records NMPC_TRACE_FIELDS doubles per iteration per scenario into a
  * device buffer readable with nmpc_read_trace (host pointer,

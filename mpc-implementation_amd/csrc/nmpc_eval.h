@@ -183,7 +183,24 @@ struct SpolIO {
   double *K, *kff, *A, *Bm, *X;
 };
 
+// DEVICE pointers, layouts and leading dimensions as nmpc_policy_rollout_batch_dev
+// (include/nmpc_amd.h); p, ubar, Xbar and e0 are required, lbg and ubg come together, and one of
+// J / viol / X / U.  No workspace: each sample's state lives in LDS
+struct RollIO {
+  const double *p, *ubar, *Xbar, *K, *lbx, *ubx, *lbg, *ubg, *e0, *w;
+  long long ld_p, ld_ubar, ld_Xbar, ld_K, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_e0, ld_w;
+  double *J, *viol;
+  int* nsat;
+  double *X, *U;
+};
+
 }  // namespace nmpc_impl
+
+// Enqueues the policy rollouts of B scenarios x M samples on `stream`: B x ceil(M / 64)
+// wavefronts, sample s of scenario b on lane s % 64 of wavefront (b, s / 64).  Same contract as
+// nmpc_eval_launch.
+int nmpc_policy_rollout_launch(const nmpc_impl::Params* dprm, int B, int M, const nmpc_impl::RollIO& io,
+                               void* stream);
 
 // Enqueues the feedback policies of B scenarios on `stream` (one wavefront per scenario, every
 // direction on it: the factorisation is done once).  Same contract as nmpc_eval_launch.

@@ -225,3 +225,6 @@ int nmpc_eval_launch(const Params* dprm, int B, const EvalIO& io, void* stream) 
 
 // the plan's feedback policy (stage gains and feedforward) in one launch: an eighth kernel of this unit
 #include "nmpc_solve_policy.hip"
+
+// disturbance rollouts of that policy on the plant, one lane per sample: a ninth kernel of this unit
+#include "nmpc_policy_rollout.hip"

@@ -6405,6 +6405,113 @@ int nmpc_solve_policy_batch(nmpc_handle* h, int32_t B, int32_t nd, const double*
   return point_staged(h, B, a, spol_launch, "solve policy");
 }
 
+// ---- disturbance rollouts of the plan's feedback policy (kernel: nmpc_policy_rollout.hip)
+struct RollArgs {
+  // p, ubar, Xbar, K, lbx, ubx, lbg, ubg, e0, w
+  const double* in[10];
+  int64_t ld[10];
+  // J, viol, X, U
+  double* out[4];
+  int32_t* nsat;
+  // filled by roll_check: the vector length each input's leading dimension must cover, and the
+  // per-scenario length of each double output
+  size_t vlen[10], olen[4];
+};
+// the argument checks of both entry points: nothing here touches the device
+static int roll_check(const nmpc_handle* h, int32_t B, int32_t M, RollArgs& a) {
+  if (!h) return fail(NMPC_E_INVALID, "null handle");
+  if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
+  if (M <= 0) return fail(NMPC_E_INVALID, "M <= 0");
+  if ((M + WAVE - 1) / WAVE > 65535) return fail(NMPC_E_INVALID, "M > 64 x 65535");
+  if (!a.in[0] || !a.in[1] || !a.in[2] || !a.in[8])
+    return fail(NMPC_E_INVALID, "required pointer is null (p, ubar, Xbar, e0)");
+  if (!a.out[0] && !a.out[1] && !a.out[2] && !a.out[3])
+    return fail(NMPC_E_INVALID, "J_out, viol_out, X_out and U_out are all null");
+  if (!a.in[6] != !a.in[7]) return fail(NMPC_E_INVALID, "lbg and ubg must be given together");
+  const Params& P = h->hp;
+  const size_t nw = P.nwE, nx = P.nxE, nu = P.nuE, N = P.N, ng = P.ng, nX = nx * (N + 1), m = M;
+  const size_t v[10] = {(size_t)P.npE, nw, nX, nu * nx * N, nw, nw, ng, ng, nx * m, nx * N * m};
+  for (int i = 0; i < 10; ++i) {
+    a.vlen[i] = v[i];
+    if (a.in[i] && a.ld[i] != 0 && a.ld[i] < (int64_t)v[i])
+      return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
+  }
+  a.olen[0] = m; a.olen[1] = m; a.olen[2] = nX * m; a.olen[3] = nw * m;
+  return NMPC_OK;
+}
+// checked arguments, DEVICE pointers: one launch, no workspace
+static int roll_enqueue(const nmpc_handle* h, int32_t B, int32_t M, const RollArgs& a, void* stream) {
+  RollIO io;
+  io.p = a.in[0]; io.ubar = a.in[1]; io.Xbar = a.in[2]; io.K = a.in[3]; io.lbx = a.in[4]; io.ubx = a.in[5];
+  io.lbg = a.in[6]; io.ubg = a.in[7]; io.e0 = a.in[8]; io.w = a.in[9];
+  io.ld_p = a.ld[0]; io.ld_ubar = a.ld[1]; io.ld_Xbar = a.ld[2]; io.ld_K = a.ld[3]; io.ld_lbx = a.ld[4];
+  io.ld_ubx = a.ld[5]; io.ld_lbg = a.ld[6]; io.ld_ubg = a.ld[7]; io.ld_e0 = a.ld[8]; io.ld_w = a.ld[9];
+  io.J = a.out[0]; io.viol = a.out[1]; io.nsat = a.nsat; io.X = a.out[2]; io.U = a.out[3];
+  const hipError_t e = (hipError_t)nmpc_policy_rollout_launch(h->dprm, (int)B, (int)M, io, stream);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("policy rollout launch: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
+int nmpc_policy_rollout_batch_dev(nmpc_handle* h, int32_t B, int32_t M, const double* p, int64_t ld_p,
+                                  const double* ubar, int64_t ld_ubar, const double* Xbar, int64_t ld_Xbar,
+                                  const double* K, int64_t ld_K, const double* lbx, int64_t ld_lbx,
+                                  const double* ubx, int64_t ld_ubx, const double* lbg, int64_t ld_lbg,
+                                  const double* ubg, int64_t ld_ubg, const double* e0, int64_t ld_e0,
+                                  const double* w, int64_t ld_w, double* J_out, double* viol_out, int32_t* nsat_out,
+                                  double* X_out, double* U_out, void* stream) {
+  RollArgs a{{p, ubar, Xbar, K, lbx, ubx, lbg, ubg, e0, w},
+             {ld_p, ld_ubar, ld_Xbar, ld_K, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_e0, ld_w},
+             {J_out, viol_out, X_out, U_out}, nsat_out};
+  if (int rc = roll_check(h, B, M, a)) return rc;
+  return roll_enqueue(h, B, M, a, stream);
+}
+
+int nmpc_policy_rollout_batch(nmpc_handle* h, int32_t B, int32_t M, const double* p, int64_t ld_p, const double* ubar,
+                              int64_t ld_ubar, const double* Xbar, int64_t ld_Xbar, const double* K, int64_t ld_K,
+                              const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx,
+                              const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg, const double* e0,
+                              int64_t ld_e0, const double* w, int64_t ld_w, double* J_out, double* viol_out,
+                              int32_t* nsat_out, double* X_out, double* U_out) {
+  RollArgs a{{p, ubar, Xbar, K, lbx, ubx, lbg, ubg, e0, w},
+             {ld_p, ld_ubar, ld_Xbar, ld_K, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_e0, ld_w},
+             {J_out, viol_out, X_out, U_out}, nsat_out};
+  if (int rc = roll_check(h, B, M, a)) return rc;
+  // staging: the inputs (absent ones take no room), the outputs, the counts; H2D, one launch,
+  // sync, D2H
+  size_t n_in[10], total = 0;
+  for (int i = 0; i < 10; ++i) {
+    n_in[i] = !a.in[i] ? 0 : (a.ld[i] == 0 ? a.vlen[i] : (size_t)(B - 1) * (size_t)a.ld[i] + a.vlen[i]);
+    total += n_in[i];
+  }
+  for (int i = 0; i < 4; ++i) total += a.out[i] ? (size_t)B * a.olen[i] : 0;
+  total += a.nsat ? ((size_t)B * (size_t)M + 1) / 2 : 0;  // B M int32 in whole doubles
+  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
+  double* q = h->dbuf;
+  RollArgs d = a;
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 10; ++i) {
+    d.in[i] = a.in[i] ? q : nullptr;
+    if (a.in[i] && e == hipSuccess) e = hipMemcpy(q, a.in[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
+    q += n_in[i];
+  }
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
+  for (int i = 0; i < 4; ++i) {
+    d.out[i] = a.out[i] ? q : nullptr;
+    q += a.out[i] ? (size_t)B * a.olen[i] : 0;
+  }
+  d.nsat = a.nsat ? (int32_t*)q : nullptr;
+  if (int rc = roll_enqueue(h, B, M, d, nullptr)) return rc;
+  e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
+  for (int i = 0; i < 4; ++i)
+    if (a.out[i] && e == hipSuccess)
+      e = hipMemcpy(a.out[i], d.out[i], (size_t)B * a.olen[i] * sizeof(double), hipMemcpyDeviceToHost);
+  if (a.nsat && e == hipSuccess)
+    e = hipMemcpy(a.nsat, d.nsat, (size_t)B * (size_t)M * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
 int nmpc_shift_dev(nmpc_handle* h, int32_t B, double* p, int64_t ld_p, const double* u_sol, double* w_out,
                    const double* v_t, const double* w_t, void* stream) {
   if (!h) return fail(NMPC_E_INVALID, "null handle");

@@ -1282,6 +1282,135 @@ class Solver:
         return {"K": raw["K"].transpose(2, 3), "kff": raw["kff"], "A": raw["A"].transpose(2, 3),
                 "B": raw["B"].transpose(2, 3), "X": raw["X"], "info": raw["info"], "delta": raw["delta"], "raw": raw}
 
+    # ---- disturbance rollouts of the policy on the plant (nmpc_policy_rollout_batch)
+    ROLLOUT_OUT = ("J", "viol", "nsat", "X", "U")
+
+    def _rollout_shapes(self, B, M):
+        N, nu, nx = self._policy_dims()
+        return {"J": (B, M), "viol": (B, M), "nsat": (B, M), "X": (B, M, N + 1, nx), "U": (B, M, N, nu)}
+
+    def policy_rollout_device(self, p, ubar, Xbar, K, e0, w=None, lbx=None, ubx=None, lbg=None, ubg=None,
+                              out: dict | None = None, want=("J", "viol", "nsat"), stream=None):
+        """M disturbance rollouts per scenario of the clamped policy u_k = clamp(ubar_k + K_k (x_k -
+        Xbar_k)) on the nonlinear plant (``nmpc_policy_rollout_batch_dev``, whose comment states
+        the formula), torch CUDA float64 tensors in and out.  ``p`` (B,np), ``ubar`` (B,nw),
+        ``lbx`` / ``ubx`` (B,nw) and ``lbg`` / ``ubg`` (B,ng) may each be shared, (n,); ``Xbar`` is
+        (B,N+1,nx) or shared (N+1,nx); ``K`` is :meth:`policy_device`'s gains -- its ``K`` view
+        (B,N,nu,nx) or the raw column-major buffer (B,N,nx,nu), or shared without the B -- or None
+        for the open-loop replay of ``ubar``; ``e0`` is (B,M,nx) or shared (M,nx), the initial-state
+        disturbances, and ``w`` (B,M,N,nx) or (M,N,nx), the process disturbances, or None.  Returns
+        a dict with the outputs named in ``want`` and those preallocated in ``out``: ``J`` (B,M),
+        ``viol`` (B,M), ``nsat`` (B,M) int32, ``X`` (B,M,N+1,nx), ``U`` (B,M,N,nu).  A NaN in a
+        sample's inputs, or in its scenario's policy, gives NaN in that sample's J and viol.
+        Enqueued on ``stream`` (default = current); never synchronises the host, reads nothing
+        back and uses no workspace of the handle."""
+        import torch  # plumbing only: device memory and streams
+
+        N, nu, nx = self._policy_dims()
+
+        def chk(t, name):
+            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), name
+
+        chk(e0, "e0")
+        assert e0.dim() in (2, 3) and e0.shape[-1] == nx, ("e0", tuple(e0.shape))
+        M = e0.shape[-2]
+        B = None
+        for t, lead in ((e0, 3), (p, 2), (ubar, 2), (Xbar, 3), (w, 4)):
+            if t is not None and t.dim() == lead:
+                B = t.shape[0]
+                break
+        if B is None:
+            raise ValueError("policy_rollout_device: no argument carries the batch size")
+
+        def dv(t, tail, name):
+            """(pointer, ld) of a (B, *tail) tensor, or of a shared one of shape tail."""
+            if t is None:
+                return [C.c_void_p(0), 0]
+            chk(t, name)
+            n = int(np.prod(tail))
+            if tuple(t.shape) == tuple(tail):
+                return [C.c_void_p(t.data_ptr()), 0]
+            assert tuple(t.shape) == (B, *tail), (name, tuple(t.shape), (B, *tail))
+            return [C.c_void_p(t.data_ptr()), n]
+
+        if K is not None and tuple(K.shape[-2:]) == (nu, nx):
+            K = K.transpose(-1, -2)  # policy_device's view back to the kernel's column-major blocks
+        if p is None or ubar is None or Xbar is None:
+            raise ValueError("p, ubar and Xbar are required")
+        if (lbg is None) != (ubg is None):
+            raise ValueError("lbg and ubg must be given together")
+        ins = (dv(p, (self.np,), "p") + dv(ubar, (self.nw,), "ubar") + dv(Xbar, (N + 1, nx), "Xbar")
+               + dv(K, (N, nx, nu), "K") + dv(lbx, (self.nw,), "lbx") + dv(ubx, (self.nw,), "ubx")
+               + dv(lbg, (self.ng,), "lbg") + dv(ubg, (self.ng,), "ubg") + dv(e0, (M, nx), "e0")
+               + dv(w, (M, N, nx), "w"))
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        shapes = self._rollout_shapes(B, M)
+        res = {}
+        with torch.cuda.stream(stream):
+            for k in self.ROLLOUT_OUT:
+                t = (out or {}).get(k)
+                dt = torch.int32 if k == "nsat" else torch.float64
+                if t is not None:
+                    assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shapes[k], k
+                elif k in want:
+                    t = torch.empty(shapes[k], dtype=dt, device=e0.device)
+                res[k] = t
+        if all(res[k] is None for k in ("J", "viol", "X", "U")):
+            raise ValueError("policy_rollout_device: one of J, viol, X, U is required")
+        ptr = [C.c_void_p(res[k].data_ptr()) if res[k] is not None else C.c_void_p(0) for k in self.ROLLOUT_OUT]
+        _lib.check(_lib.lib().nmpc_policy_rollout_batch_dev(self._h, B, M, *ins, *ptr, C.c_void_p(stream.cuda_stream)))
+        return {k: v for k, v in res.items() if v is not None}
+
+    def policy_rollout(self, p, ubar, Xbar, K, e0, w=None, lbx=None, ubx=None, lbg=None, ubg=None,
+                       want=("J", "viol", "nsat", "X", "U")):
+        """:meth:`policy_rollout_device` through the host entry point
+        (``nmpc_policy_rollout_batch``), NumPy arrays in the same scenario-major shapes: ``p``
+        (B,np), ``ubar`` (B,nw), ``Xbar`` (B,N+1,nx), ``K`` (B,N,nu,nx) (row-major blocks, as
+        :meth:`policy_fused` returns them) or None, ``e0`` (B,M,nx), ``w`` (B,M,N,nx) or None, the
+        bounds (B,n) -- each may be shared (without the B).  Returns the outputs named in ``want``."""
+        N, nu, nx = self._policy_dims()
+        e0 = np.ascontiguousarray(e0, dtype=np.float64)
+        if e0.ndim not in (2, 3) or e0.shape[-1] != nx:
+            raise ValueError(f"e0: expected (M,{nx}) or (B,M,{nx}), got shape {e0.shape}")
+        M = e0.shape[-2]
+        if K is not None:
+            K = np.asarray(K, dtype=np.float64)
+            if K.shape[-2:] != (nu, nx):
+                raise ValueError(f"K: expected blocks of ({nu},{nx}), got shape {K.shape}")
+            K = np.swapaxes(K, -1, -2)  # to the kernel's column-major blocks
+        fields = (("p", p, (self.np,)), ("ubar", ubar, (self.nw,)), ("Xbar", Xbar, (N + 1, nx)), ("K", K, (N, nx, nu)),
+                  ("lbx", lbx, (self.nw,)), ("ubx", ubx, (self.nw,)), ("lbg", lbg, (self.ng,)), ("ubg", ubg, (self.ng,)),
+                  ("e0", e0, (M, nx)), ("w", w, (M, N, nx)))
+        arrs, B = [], None
+        for name, a, tail in fields:
+            if a is None:
+                if name in ("p", "ubar", "Xbar"):
+                    raise ValueError(f"{name} is required")
+                arrs.append((None, 0))
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape == tail:
+                arrs.append((a, 0))
+                continue
+            if a.shape[1:] != tail or B not in (None, a.shape[0]):
+                raise ValueError(f"{name}: expected {tail} or (B,) + {tail}, got shape {a.shape}")
+            B = a.shape[0]
+            arrs.append((a, int(np.prod(tail))))
+        if B is None:
+            raise ValueError("policy_rollout: no argument carries the batch size")
+        if (lbg is None) != (ubg is None):
+            raise ValueError("lbg and ubg must be given together")
+        shapes = self._rollout_shapes(B, M)
+        res = {k: np.empty(shapes[k], dtype=np.int32 if k == "nsat" else np.float64) for k in self.ROLLOUT_OUT
+               if k in want}
+        if not any(k in res for k in ("J", "viol", "X", "U")):
+            raise ValueError("policy_rollout: one of J, viol, X, U is required")
+        ptr = [None if k not in res else (res[k].ctypes.data_as(_IP) if k == "nsat" else _dptr(res[k]))
+               for k in self.ROLLOUT_OUT]
+        _lib.check(_lib.lib().nmpc_policy_rollout_batch(self._h, B, M, *self._flat_ins(arrs), *ptr))
+        return res
+
     def shift_device(self, p, u_sol, w_out, v_t, w_t, stream=None):
         """Closed-loop shift on device (Python/NMPC_TT.py:13-30), see nmpc_shift_dev."""
         import torch

@@ -5,7 +5,9 @@ feedforward kff_k per parameter direction and the plan's states X*_k; :func:`app
 
     u_k(x, c) = u*_k + K_k (x - X*_k) + sum_d kff_k^(d) c_d
 
-with torch ops on the caller's stream: nothing is copied to the host."""
+with torch ops on the caller's stream: nothing is copied to the host.  :func:`rollout` runs that
+policy, clamped, on the nonlinear plant for many disturbance samples per scenario in one launch
+(``Solver.policy_rollout_device``): what it costs and whether it keeps the rows."""
 from __future__ import annotations
 
 
@@ -38,3 +40,34 @@ def apply(pol: dict, sol: dict, k: int, x_meas, c=None, lbx=None, ubx=None):
         u = torch.minimum(u, stage(ubx))
     bad = (pol["info"] != 0).unsqueeze(1)
     return torch.where(bad, torch.full_like(u, float("nan")), u)
+
+
+def rollout(solver, pol: dict, sol: dict, p, e0, w=None, c=None, lbx=None, ubx=None, lbg=None, ubg=None,
+            feedback: bool = True, out: dict | None = None, want=("J", "viol", "nsat"), stream=None):
+    """M disturbance rollouts per scenario of the clamped policy on the nonlinear plant, in one
+    launch (``Solver.policy_rollout_device``): what the policy costs and whether it keeps the rows
+    when the state starts ``e0`` (B, M, nx) away from the plan and is pushed by ``w`` (B, M, N, nx)
+    at every stage (None: no process disturbance).
+
+    ``pol`` is the dict of ``Solver.policy_device``, ``sol["x"]`` (B, nw) the plan's controls and
+    ``p`` (B, np) the parameters the plant runs with -- after a parameter move along the policy's
+    directions the moved ones, with ``c`` (B, nd) or (nd,) the move's coefficients: the nominal
+    controls are then ubar = u* + sum_d kff^(d) c_d.  ``feedback=False`` replays ubar open loop
+    (no gains), the baseline the feedback is measured against.  ``lbx`` / ``ubx`` clamp the
+    controls, ``lbg`` / ``ubg`` are the rows' bounds for ``viol``.  Returns the dict of
+    ``Solver.policy_rollout_device``: ``J``, ``viol``, ``nsat`` (B, M) and, when asked for in
+    ``want`` or preallocated in ``out``, ``X`` (B, M, N+1, nx) and ``U`` (B, M, N, nu).  A scenario
+    whose ``info`` is not 0 has NaN gains and plan, hence NaN J and viol.  Nothing is copied to the
+    host and nothing synchronises."""
+    import torch
+
+    ubar = sol["x"]
+    if c is not None:
+        kff = pol["kff"]
+        if kff is None:
+            raise ValueError("the policy holds no feedforward: it was formed without directions")
+        cc = c if c.dim() == 2 else c.unsqueeze(0).expand(kff.shape[0], -1)
+        ubar = ubar + torch.einsum("bdn,bd->bn", kff.reshape(kff.shape[0], kff.shape[1], -1), cc)
+    raw = pol["raw"]
+    return solver.policy_rollout_device(p, ubar.contiguous(), raw["X"], raw["K"] if feedback else None, e0, w=w,
+                                        lbx=lbx, ubx=ubx, lbg=lbg, ubg=ubg, out=out, want=want, stream=stream)
