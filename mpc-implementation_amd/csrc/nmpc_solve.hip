@@ -5642,44 +5642,131 @@ int nmpc_solve_batch(nmpc_handle* h, int32_t B, const double* x0, int64_t ld_x0,
   return NMPC_OK;
 }
 
-// ---- evaluation at given points (kernel: nmpc_eval.hip)
-struct EvalArgs {
-  const double *x, *p, *lam_g, *lam_x, *lbx, *ubx, *lbg, *ubg;
-  int64_t ld_x, ld_p, ld_lam_g, ld_lam_x, ld_lbx, ld_ubx, ld_lbg, ld_ubg;
-  double *f, *g, *X, *grad_f, *grad_l, *kkt;
+// ---- the batched entry points at given points.  One argument block, one check, one enqueue and
+// one staging routine serve the nine entry-point pairs (X_batch on host pointers, X_batch_dev on
+// device pointers); a pair adds its own rules, its table of lengths and its launch callback
+struct CallArgs {
+  // the inputs in the C argument order (absent ones null) and their leading dimensions
+  const double* in[12];
+  int64_t ld[12];
+  int nin;
+  // the double outputs in the C argument order
+  double* out[6];
+  int nout;
+  // the optional int32 output (info, nsat) and its per-scenario length
+  int32_t* iout;
+  size_t ilen;
+  int32_t n;  // directions, seeds, right-hand sides or samples
+  double obj_factor;
+  // filled by check: the vector length each input's leading dimension must cover, and the
+  // per-scenario length of each double output
+  size_t vlen[12], olen[6];
 };
-// the argument checks of both entry points: nothing here touches the device
-static int eval_check(const nmpc_handle* h, int32_t B, const EvalArgs& a) {
+// fills the kernel's IO block from checked arguments (DEVICE pointers) and launches
+typedef int (*Launch)(const nmpc_handle* h, int32_t B, const CallArgs& a, void* stream);
+typedef void (*Lengths)(const Params& P, CallArgs& a);
+
+static bool all_null(const double* const* q, int n) {
+  for (int i = 0; i < n; ++i)
+    if (q[i]) return false;
+  return true;
+}
+static void set_lens(size_t* dst, std::initializer_list<size_t> v) {
+  for (size_t x : v) *dst++ = x;
+}
+struct Dims { size_t nw, ng, np, nX, n; };
+static Dims dims(const Params& P, const CallArgs& a) {
+  return {(size_t)P.nwE, (size_t)P.ng, (size_t)P.npE, (size_t)P.nxE * (P.N + 1), (size_t)a.n};
+}
+
+// the argument checks of an entry-point pair, in the order of their messages: nothing here
+// touches the device.  count_err and own_err are the pair's own rules (null: met); bit i of req
+// marks input i as required; lengths fills vlen and olen
+static int check(const nmpc_handle* h, int32_t B, const char* count_err, CallArgs& a, unsigned req,
+                 const char* req_err, const char* own_err, Lengths lengths) {
   if (!h) return fail(NMPC_E_INVALID, "null handle");
   if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
-  if (!a.x || !a.p) return fail(NMPC_E_INVALID, "required pointer is null (x, p)");
-  if (!a.f && !a.g && !a.X && !a.grad_f && !a.grad_l && !a.kkt)
-    return fail(NMPC_E_INVALID, "every output pointer is null");
-  if (a.kkt && (!a.lbx || !a.ubx || !a.lbg || !a.ubg))
-    return fail(NMPC_E_INVALID, "kkt_out needs lbx, ubx, lbg and ubg");
-  const Params& P = h->hp;
-  auto bad = [](const double* q, int64_t ld, int n) { return q && ld != 0 && ld < n; };
-  if (bad(a.x, a.ld_x, P.nwE) || bad(a.p, a.ld_p, P.npE) || bad(a.lam_g, a.ld_lam_g, P.ng) ||
-      bad(a.lam_x, a.ld_lam_x, P.nwE) || bad(a.lbx, a.ld_lbx, P.nwE) || bad(a.ubx, a.ld_ubx, P.nwE) ||
-      bad(a.lbg, a.ld_lbg, P.ng) || bad(a.ubg, a.ld_ubg, P.ng))
-    return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
+  if (count_err) return fail(NMPC_E_INVALID, count_err);
+  for (int i = 0; i < a.nin; ++i)
+    if ((req >> i & 1u) && !a.in[i]) return fail(NMPC_E_INVALID, req_err);
+  if (own_err) return fail(NMPC_E_INVALID, own_err);
+  lengths(h->hp, a);
+  for (int i = 0; i < a.nin; ++i)
+    if (a.in[i] && a.ld[i] != 0 && a.ld[i] < (int64_t)a.vlen[i])
+      return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
   return NMPC_OK;
 }
-// checked arguments, DEVICE pointers: workspace from the handle (sized like a solve's, grown
-// only when it does not cover B yet), then one launch
-static int eval_enqueue(nmpc_handle* h, int32_t B, const EvalArgs& a, void* stream) {
-  const int per = h->ws_doubles > kEvalWs ? h->ws_doubles : kEvalWs;
-  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
-  EvalIO io;
-  io.x = a.x; io.p = a.p; io.lam_g = a.lam_g; io.lam_x = a.lam_x;
-  io.lbx = a.lbx; io.ubx = a.ubx; io.lbg = a.lbg; io.ubg = a.ubg;
-  io.ld_x = a.ld_x; io.ld_p = a.ld_p; io.ld_lam_g = a.ld_lam_g; io.ld_lam_x = a.ld_lam_x;
-  io.ld_lbx = a.ld_lbx; io.ld_ubx = a.ld_ubx; io.ld_lbg = a.ld_lbg; io.ld_ubg = a.ld_ubg;
-  io.f = a.f; io.g = a.g; io.X = a.X; io.grad_f = a.grad_f; io.grad_l = a.grad_l; io.kkt = a.kkt;
-  io.ws = h->dws;
-  const hipError_t e = (hipError_t)nmpc_eval_launch(h->dprm, (int)B, io, stream);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("evaluation launch: ") + hipGetErrorString(e));
+// doubles of workspace per scenario of a kernel that needs ws of them: the handle's is sized
+// like a solve's
+static int ws_per(const nmpc_handle* h, int ws) { return h->ws_doubles > ws ? h->ws_doubles : ws; }
+// checked arguments, DEVICE pointers: workspace from the handle (grown only when it does not
+// cover B yet; ws = 0: the kernel uses none), then one launch
+static int enqueue(nmpc_handle* h, int32_t B, const CallArgs& a, void* stream, Launch launch, const char* what,
+                   int ws) {
+  if (ws)
+    if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * ws_per(h, ws) * sizeof(double), "workspace"))
+      return rc;
+  const hipError_t e = (hipError_t)launch(h, B, a, stream);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
   return NMPC_OK;
+}
+// checked arguments, HOST pointers.  Staging: the inputs (absent ones take no room), the double
+// outputs, the int32 output in whole doubles; H2D, one launch, sync, D2H
+static int staged(nmpc_handle* h, int32_t B, const CallArgs& a, Launch launch, const char* what, int ws) {
+  size_t n_in[12], total = 0;
+  for (int i = 0; i < a.nin; ++i) {
+    n_in[i] = !a.in[i] ? 0 : (a.ld[i] == 0 ? a.vlen[i] : (size_t)(B - 1) * (size_t)a.ld[i] + a.vlen[i]);
+    total += n_in[i];
+  }
+  for (int i = 0; i < a.nout; ++i) total += a.out[i] ? (size_t)B * a.olen[i] : 0;
+  total += a.iout ? ((size_t)B * a.ilen + 1) / 2 : 0;
+  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
+  double* q = h->dbuf;
+  CallArgs d = a;
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < a.nin; ++i) {
+    d.in[i] = a.in[i] ? q : nullptr;
+    if (a.in[i] && e == hipSuccess) e = hipMemcpy(q, a.in[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
+    q += n_in[i];
+  }
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
+  for (int i = 0; i < a.nout; ++i) {
+    d.out[i] = a.out[i] ? q : nullptr;
+    q += a.out[i] ? (size_t)B * a.olen[i] : 0;
+  }
+  d.iout = a.iout ? (int32_t*)q : nullptr;
+  if (int rc = enqueue(h, B, d, nullptr, launch, what, ws)) return rc;
+  e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
+  for (int i = 0; i < a.nout; ++i)
+    if (a.out[i] && e == hipSuccess)
+      e = hipMemcpy(a.out[i], d.out[i], (size_t)B * a.olen[i] * sizeof(double), hipMemcpyDeviceToHost);
+  if (a.iout && e == hipSuccess)
+    e = hipMemcpy(a.iout, d.iout, (size_t)B * a.ilen * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
+  return NMPC_OK;
+}
+
+// ---- evaluation at given points (kernel: nmpc_eval.hip)
+static int eval_check(const nmpc_handle* h, int32_t B, CallArgs& a) {
+  const char* own = nullptr;
+  if (all_null(a.out, 6)) own = "every output pointer is null";
+  else if (a.out[5] && !(a.in[4] && a.in[5] && a.in[6] && a.in[7])) own = "kkt_out needs lbx, ubx, lbg and ubg";
+  return check(h, B, nullptr, a, 0x3, "required pointer is null (x, p)", own, [](const Params& P, CallArgs& a) {
+    const auto [nw, ng, np, nX, n] = dims(P, a);
+    set_lens(a.vlen, {nw, np, ng, nw, nw, nw, ng, ng});
+    set_lens(a.olen, {1, ng, nX, nw, nw, 5});
+  });
+}
+static int eval_launch(const nmpc_handle* h, int32_t B, const CallArgs& a, void* stream) {
+  EvalIO io;
+  io.x = a.in[0]; io.p = a.in[1]; io.lam_g = a.in[2]; io.lam_x = a.in[3];
+  io.lbx = a.in[4]; io.ubx = a.in[5]; io.lbg = a.in[6]; io.ubg = a.in[7];
+  io.ld_x = a.ld[0]; io.ld_p = a.ld[1]; io.ld_lam_g = a.ld[2]; io.ld_lam_x = a.ld[3];
+  io.ld_lbx = a.ld[4]; io.ld_ubx = a.ld[5]; io.ld_lbg = a.ld[6]; io.ld_ubg = a.ld[7];
+  io.f = a.out[0]; io.g = a.out[1]; io.X = a.out[2]; io.grad_f = a.out[3]; io.grad_l = a.out[4]; io.kkt = a.out[5];
+  io.ws = h->dws;
+  return nmpc_eval_launch(h->dprm, (int)B, io, stream);
 }
 
 int nmpc_eval_batch_dev(nmpc_handle* h, int32_t B, const double* x, int64_t ld_x, const double* p, int64_t ld_p,
@@ -5687,10 +5774,11 @@ int nmpc_eval_batch_dev(nmpc_handle* h, int32_t B, const double* x, int64_t ld_x
                         const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx, const double* lbg,
                         int64_t ld_lbg, const double* ubg, int64_t ld_ubg, double* f_out, double* g_out,
                         double* X_out, double* grad_f_out, double* grad_l_out, double* kkt_out, void* stream) {
-  const EvalArgs a{x, p, lam_g, lam_x, lbx, ubx, lbg, ubg, ld_x, ld_p, ld_lam_g, ld_lam_x, ld_lbx, ld_ubx, ld_lbg,
-                   ld_ubg, f_out, g_out, X_out, grad_f_out, grad_l_out, kkt_out};
+  CallArgs a{{x, p, lam_g, lam_x, lbx, ubx, lbg, ubg},
+             {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_lbx, ld_ubx, ld_lbg, ld_ubg}, 8,
+             {f_out, g_out, X_out, grad_f_out, grad_l_out, kkt_out}, 6};
   if (int rc = eval_check(h, B, a)) return rc;
-  return eval_enqueue(h, B, a, stream);
+  return enqueue(h, B, a, stream, eval_launch, "evaluation", kEvalWs);
 }
 
 int nmpc_eval_batch(nmpc_handle* h, int32_t B, const double* x, int64_t ld_x, const double* p, int64_t ld_p,
@@ -5698,70 +5786,21 @@ int nmpc_eval_batch(nmpc_handle* h, int32_t B, const double* x, int64_t ld_x, co
                     int64_t ld_lbx, const double* ubx, int64_t ld_ubx, const double* lbg, int64_t ld_lbg,
                     const double* ubg, int64_t ld_ubg, double* f_out, double* g_out, double* X_out,
                     double* grad_f_out, double* grad_l_out, double* kkt_out) {
-  const EvalArgs a{x, p, lam_g, lam_x, lbx, ubx, lbg, ubg, ld_x, ld_p, ld_lam_g, ld_lam_x, ld_lbx, ld_ubx, ld_lbg,
-                   ld_ubg, f_out, g_out, X_out, grad_f_out, grad_l_out, kkt_out};
+  CallArgs a{{x, p, lam_g, lam_x, lbx, ubx, lbg, ubg},
+             {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_lbx, ld_ubx, ld_lbg, ld_ubg}, 8,
+             {f_out, g_out, X_out, grad_f_out, grad_l_out, kkt_out}, 6};
   if (int rc = eval_check(h, B, a)) return rc;
-  const Params& P = h->hp;
-  const size_t nw = P.nwE, ng = P.ng, np = P.npE, nX = (size_t)P.nxE * (P.N + 1);
-  // staging: the eight inputs (absent ones take no room), then the six outputs
-  const double* src[8] = {x, p, lam_g, lam_x, lbx, ubx, lbg, ubg};
-  const int64_t ld[8] = {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_lbx, ld_ubx, ld_lbg, ld_ubg};
-  const size_t vlen[8] = {nw, np, ng, nw, nw, nw, ng, ng};
-  double* hout[6] = {f_out, g_out, X_out, grad_f_out, grad_l_out, kkt_out};
-  const size_t olen[6] = {1, ng, nX, nw, nw, 5};
-  size_t n_in[8], total = 0;
-  for (int i = 0; i < 8; ++i) {
-    n_in[i] = !src[i] ? 0 : (ld[i] == 0 ? vlen[i] : (size_t)(B - 1) * (size_t)ld[i] + vlen[i]);
-    total += n_in[i];
-  }
-  for (int i = 0; i < 6; ++i) total += hout[i] ? (size_t)B * olen[i] : 0;
-  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
-  double* q = h->dbuf;
-  const double* din[8];
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 8; ++i) {
-    din[i] = src[i] ? q : nullptr;
-    if (src[i] && e == hipSuccess) e = hipMemcpy(q, src[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
-    q += n_in[i];
-  }
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
-  double* dout[6];
-  for (int i = 0; i < 6; ++i) {
-    dout[i] = hout[i] ? q : nullptr;
-    q += hout[i] ? (size_t)B * olen[i] : 0;
-  }
-  const EvalArgs d{din[0], din[1], din[2], din[3], din[4], din[5], din[6], din[7], ld_x, ld_p, ld_lam_g, ld_lam_x,
-                   ld_lbx, ld_ubx, ld_lbg, ld_ubg, dout[0], dout[1], dout[2], dout[3], dout[4], dout[5]};
-  if (int rc = eval_enqueue(h, B, d, nullptr)) return rc;
-  e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
-  for (int i = 0; i < 6; ++i)
-    if (hout[i] && e == hipSuccess)
-      e = hipMemcpy(hout[i], dout[i], (size_t)B * olen[i] * sizeof(double), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
-  return NMPC_OK;
+  return staged(h, B, a, eval_launch, "evaluation", kEvalWs);
 }
 
 // ---- Jacobian- and Hessian-vector products at given points (kernel: nmpc_products.hip)
-struct ProdArgs {
-  const double *x, *p, *lam_g, *v;
-  int64_t ld_x, ld_p, ld_lam_g, ld_v;
-  double obj_factor;
-  double *jv, *hv, *dX;
-};
-// the argument checks of both entry points: nothing here touches the device
-static int prod_check(const nmpc_handle* h, int32_t B, int32_t nv, const ProdArgs& a) {
-  if (!h) return fail(NMPC_E_INVALID, "null handle");
-  if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
-  if (nv <= 0) return fail(NMPC_E_INVALID, "nv <= 0");
-  if (!a.x || !a.p || !a.v) return fail(NMPC_E_INVALID, "required pointer is null (x, p, v)");
-  if (!a.jv && !a.hv && !a.dX) return fail(NMPC_E_INVALID, "every output pointer is null");
-  const Params& P = h->hp;
-  auto bad = [](const double* q, int64_t ld, int64_t n) { return q && ld != 0 && ld < n; };
-  if (bad(a.x, a.ld_x, P.nwE) || bad(a.p, a.ld_p, P.npE) || bad(a.lam_g, a.ld_lam_g, P.ng) ||
-      bad(a.v, a.ld_v, (int64_t)P.nwE * nv))
-    return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
-  return NMPC_OK;
+static int prod_check(const nmpc_handle* h, int32_t B, CallArgs& a) {
+  return check(h, B, a.n <= 0 ? "nv <= 0" : nullptr, a, 0xb, "required pointer is null (x, p, v)",
+               all_null(a.out, 3) ? "every output pointer is null" : nullptr, [](const Params& P, CallArgs& a) {
+                 const auto [nw, ng, np, nX, nv] = dims(P, a);
+                 set_lens(a.vlen, {nw, np, ng, nw * nv});
+                 set_lens(a.olen, {ng * nv, nw * nv, nX * nv});
+               });
 }
 // wavefronts per scenario of a products launch: `per` doubles of workspace per scenario hold
 // per / slice of them, nv directions occupy at most nv
@@ -5778,118 +5817,59 @@ static int prod_chunks(int per, int slice, int32_t B, int32_t nv) {
   if (chunks < 1) chunks = 1;
   return chunks;
 }
-// checked arguments, DEVICE pointers: workspace from the handle (sized like a solve's, grown
-// only when it does not cover B yet), then one launch.  A scenario's directions are dealt to
-// as many wavefronts as the class's per-scenario workspace holds slices for.
-static int prod_enqueue(nmpc_handle* h, int32_t B, int32_t nv, const ProdArgs& a, void* stream) {
-  const int per = h->ws_doubles > kProdWs ? h->ws_doubles : kProdWs;
-  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
-  const int chunks = prod_chunks(per, kProdWs, B, nv);
+// a scenario's directions are dealt to as many wavefronts as the class's per-scenario workspace
+// holds slices for
+static int prod_launch(const nmpc_handle* h, int32_t B, const CallArgs& a, void* stream) {
   ProdIO io;
-  io.x = a.x; io.p = a.p; io.lam_g = a.lam_g; io.v = a.v;
-  io.ld_x = a.ld_x; io.ld_p = a.ld_p; io.ld_lam_g = a.ld_lam_g; io.ld_v = a.ld_v;
-  io.obj_factor = a.obj_factor; io.nv = nv;
-  io.jv = a.jv; io.hv = a.hv; io.dX = a.dX;
+  io.x = a.in[0]; io.p = a.in[1]; io.lam_g = a.in[2]; io.v = a.in[3];
+  io.ld_x = a.ld[0]; io.ld_p = a.ld[1]; io.ld_lam_g = a.ld[2]; io.ld_v = a.ld[3];
+  io.obj_factor = a.obj_factor; io.nv = a.n;
+  io.jv = a.out[0]; io.hv = a.out[1]; io.dX = a.out[2];
   io.ws = h->dws;
-  const hipError_t e = (hipError_t)nmpc_products_launch(h->dprm, (int)B, chunks, io, stream);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("products launch: ") + hipGetErrorString(e));
-  return NMPC_OK;
+  return nmpc_products_launch(h->dprm, (int)B, prod_chunks(ws_per(h, kProdWs), kProdWs, B, a.n), io, stream);
 }
 
 int nmpc_products_batch_dev(nmpc_handle* h, int32_t B, int32_t nv, const double* x, int64_t ld_x, const double* p,
                             int64_t ld_p, const double* lam_g, int64_t ld_lam_g, double obj_factor,
                             const double* v, int64_t ld_v, double* jv_out, double* hv_out, double* dX_out,
                             void* stream) {
-  const ProdArgs a{x, p, lam_g, v, ld_x, ld_p, ld_lam_g, ld_v, obj_factor, jv_out, hv_out, dX_out};
-  if (int rc = prod_check(h, B, nv, a)) return rc;
-  return prod_enqueue(h, B, nv, a, stream);
+  CallArgs a{{x, p, lam_g, v}, {ld_x, ld_p, ld_lam_g, ld_v}, 4, {jv_out, hv_out, dX_out}, 3, nullptr, 0, nv,
+             obj_factor};
+  if (int rc = prod_check(h, B, a)) return rc;
+  return enqueue(h, B, a, stream, prod_launch, "products", kProdWs);
 }
 
 int nmpc_products_batch(nmpc_handle* h, int32_t B, int32_t nv, const double* x, int64_t ld_x, const double* p,
                         int64_t ld_p, const double* lam_g, int64_t ld_lam_g, double obj_factor, const double* v,
                         int64_t ld_v, double* jv_out, double* hv_out, double* dX_out) {
-  const ProdArgs a{x, p, lam_g, v, ld_x, ld_p, ld_lam_g, ld_v, obj_factor, jv_out, hv_out, dX_out};
-  if (int rc = prod_check(h, B, nv, a)) return rc;
-  const Params& P = h->hp;
-  const size_t nw = P.nwE, ng = P.ng, np = P.npE, nX = (size_t)P.nxE * (P.N + 1);
-  // staging: the four inputs (an absent lam_g takes no room), then the three outputs
-  const double* src[4] = {x, p, lam_g, v};
-  const int64_t ld[4] = {ld_x, ld_p, ld_lam_g, ld_v};
-  const size_t vlen[4] = {nw, np, ng, nw * (size_t)nv};
-  double* hout[3] = {jv_out, hv_out, dX_out};
-  const size_t olen[3] = {ng * (size_t)nv, nw * (size_t)nv, nX * (size_t)nv};
-  size_t n_in[4], total = 0;
-  for (int i = 0; i < 4; ++i) {
-    n_in[i] = !src[i] ? 0 : (ld[i] == 0 ? vlen[i] : (size_t)(B - 1) * (size_t)ld[i] + vlen[i]);
-    total += n_in[i];
-  }
-  for (int i = 0; i < 3; ++i) total += hout[i] ? (size_t)B * olen[i] : 0;
-  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
-  double* q = h->dbuf;
-  const double* din[4];
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 4; ++i) {
-    din[i] = src[i] ? q : nullptr;
-    if (src[i] && e == hipSuccess) e = hipMemcpy(q, src[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
-    q += n_in[i];
-  }
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
-  double* dout[3];
-  for (int i = 0; i < 3; ++i) {
-    dout[i] = hout[i] ? q : nullptr;
-    q += hout[i] ? (size_t)B * olen[i] : 0;
-  }
-  const ProdArgs d{din[0], din[1], din[2], din[3], ld_x, ld_p, ld_lam_g, ld_v, obj_factor, dout[0], dout[1], dout[2]};
-  if (int rc = prod_enqueue(h, B, nv, d, nullptr)) return rc;
-  e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
-  for (int i = 0; i < 3; ++i)
-    if (hout[i] && e == hipSuccess)
-      e = hipMemcpy(hout[i], dout[i], (size_t)B * olen[i] * sizeof(double), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
-  return NMPC_OK;
+  CallArgs a{{x, p, lam_g, v}, {ld_x, ld_p, ld_lam_g, ld_v}, 4, {jv_out, hv_out, dX_out}, 3, nullptr, 0, nv,
+             obj_factor};
+  if (int rc = prod_check(h, B, a)) return rc;
+  return staged(h, B, a, prod_launch, "products", kProdWs);
 }
 
 // ---- condensed KKT solves at given points (kernel: nmpc_kkt.hip)
-struct KktArgs {
-  const double *x, *p, *lam_g, *sigma_x, *sigma_s, *delta, *r_w, *r_g;
-  int64_t ld_x, ld_p, ld_lam_g, ld_sigma_x, ld_sigma_s, ld_delta, ld_r_w, ld_r_g;
-  double obj_factor;
-  double *dw, *dX, *jdw;
-  int32_t* info;
-};
-// the argument checks of both entry points: nothing here touches the device
-static int kkt_check(const nmpc_handle* h, int32_t B, int32_t nr, const KktArgs& a) {
-  if (!h) return fail(NMPC_E_INVALID, "null handle");
-  if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
-  if (nr <= 0) return fail(NMPC_E_INVALID, "nr <= 0");
-  if (!a.x || !a.p) return fail(NMPC_E_INVALID, "required pointer is null (x, p)");
-  if (!a.r_w && !a.r_g) return fail(NMPC_E_INVALID, "both right-hand sides are null (r_w, r_g)");
-  if (!a.dw && !a.dX && !a.jdw) return fail(NMPC_E_INVALID, "every output pointer is null (dw, dX, jdw)");
-  const Params& P = h->hp;
-  auto bad = [](const double* q, int64_t ld, int64_t n) { return q && ld != 0 && ld < n; };
-  if (bad(a.x, a.ld_x, P.nwE) || bad(a.p, a.ld_p, P.npE) || bad(a.lam_g, a.ld_lam_g, P.ng) ||
-      bad(a.sigma_x, a.ld_sigma_x, P.nwE) || bad(a.sigma_s, a.ld_sigma_s, P.ng) || bad(a.delta, a.ld_delta, 1) ||
-      bad(a.r_w, a.ld_r_w, (int64_t)P.nwE * nr) || bad(a.r_g, a.ld_r_g, (int64_t)P.ng * nr))
-    return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
-  return NMPC_OK;
+static int kkt_check(const nmpc_handle* h, int32_t B, CallArgs& a) {
+  const char* own = nullptr;
+  if (!a.in[6] && !a.in[7]) own = "both right-hand sides are null (r_w, r_g)";
+  else if (all_null(a.out, 3)) own = "every output pointer is null (dw, dX, jdw)";
+  return check(h, B, a.n <= 0 ? "nr <= 0" : nullptr, a, 0x3, "required pointer is null (x, p)", own,
+               [](const Params& P, CallArgs& a) {
+                 const auto [nw, ng, np, nX, nr] = dims(P, a);
+                 set_lens(a.vlen, {nw, np, ng, nw, ng, 1, nw * nr, ng * nr});
+                 set_lens(a.olen, {nw * nr, nX * nr, ng * nr});
+               });
 }
-// checked arguments, DEVICE pointers: workspace from the handle (sized like a solve's, grown
-// only when it does not cover B yet), then one launch
-static int kkt_enqueue(nmpc_handle* h, int32_t B, int32_t nr, const KktArgs& a, void* stream) {
-  const int per = h->ws_doubles > kKktWs ? h->ws_doubles : kKktWs;
-  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
+static int kkt_launch(const nmpc_handle* h, int32_t B, const CallArgs& a, void* stream) {
   KktIO io;
-  io.x = a.x; io.p = a.p; io.lam_g = a.lam_g; io.sigma_x = a.sigma_x; io.sigma_s = a.sigma_s; io.delta = a.delta;
-  io.r_w = a.r_w; io.r_g = a.r_g;
-  io.ld_x = a.ld_x; io.ld_p = a.ld_p; io.ld_lam_g = a.ld_lam_g; io.ld_sigma_x = a.ld_sigma_x;
-  io.ld_sigma_s = a.ld_sigma_s; io.ld_delta = a.ld_delta; io.ld_r_w = a.ld_r_w; io.ld_r_g = a.ld_r_g;
-  io.obj_factor = a.obj_factor; io.nr = nr;
-  io.dw = a.dw; io.dX = a.dX; io.jdw = a.jdw; io.info = a.info;
+  io.x = a.in[0]; io.p = a.in[1]; io.lam_g = a.in[2]; io.sigma_x = a.in[3]; io.sigma_s = a.in[4]; io.delta = a.in[5];
+  io.r_w = a.in[6]; io.r_g = a.in[7];
+  io.ld_x = a.ld[0]; io.ld_p = a.ld[1]; io.ld_lam_g = a.ld[2]; io.ld_sigma_x = a.ld[3];
+  io.ld_sigma_s = a.ld[4]; io.ld_delta = a.ld[5]; io.ld_r_w = a.ld[6]; io.ld_r_g = a.ld[7];
+  io.obj_factor = a.obj_factor; io.nr = a.n;
+  io.dw = a.out[0]; io.dX = a.out[1]; io.jdw = a.out[2]; io.info = a.iout;
   io.ws = h->dws;
-  const hipError_t e = (hipError_t)nmpc_kkt_launch(h->dprm, (int)B, io, stream);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("KKT solve launch: ") + hipGetErrorString(e));
-  return NMPC_OK;
+  return nmpc_kkt_launch(h->dprm, (int)B, io, stream);
 }
 
 int nmpc_kkt_solve_batch_dev(nmpc_handle* h, int32_t B, int32_t nr, const double* x, int64_t ld_x, const double* p,
@@ -5898,10 +5878,11 @@ int nmpc_kkt_solve_batch_dev(nmpc_handle* h, int32_t B, int32_t nr, const double
                              const double* delta, int64_t ld_delta, const double* r_w, int64_t ld_r_w,
                              const double* r_g, int64_t ld_r_g, double* dw_out, double* dX_out, double* jdw_out,
                              int32_t* info_out, void* stream) {
-  const KktArgs a{x, p, lam_g, sigma_x, sigma_s, delta, r_w, r_g, ld_x, ld_p, ld_lam_g, ld_sigma_x, ld_sigma_s,
-                  ld_delta, ld_r_w, ld_r_g, obj_factor, dw_out, dX_out, jdw_out, info_out};
-  if (int rc = kkt_check(h, B, nr, a)) return rc;
-  return kkt_enqueue(h, B, nr, a, stream);
+  CallArgs a{{x, p, lam_g, sigma_x, sigma_s, delta, r_w, r_g},
+             {ld_x, ld_p, ld_lam_g, ld_sigma_x, ld_sigma_s, ld_delta, ld_r_w, ld_r_g}, 8,
+             {dw_out, dX_out, jdw_out}, 3, info_out, 1, nr, obj_factor};
+  if (int rc = kkt_check(h, B, a)) return rc;
+  return enqueue(h, B, a, stream, kkt_launch, "KKT solve", kKktWs);
 }
 
 int nmpc_kkt_solve_batch(nmpc_handle* h, int32_t B, int32_t nr, const double* x, int64_t ld_x, const double* p,
@@ -5909,187 +5890,80 @@ int nmpc_kkt_solve_batch(nmpc_handle* h, int32_t B, int32_t nr, const double* x,
                          const double* sigma_x, int64_t ld_sigma_x, const double* sigma_s, int64_t ld_sigma_s,
                          const double* delta, int64_t ld_delta, const double* r_w, int64_t ld_r_w, const double* r_g,
                          int64_t ld_r_g, double* dw_out, double* dX_out, double* jdw_out, int32_t* info_out) {
-  const KktArgs a{x, p, lam_g, sigma_x, sigma_s, delta, r_w, r_g, ld_x, ld_p, ld_lam_g, ld_sigma_x, ld_sigma_s,
-                  ld_delta, ld_r_w, ld_r_g, obj_factor, dw_out, dX_out, jdw_out, info_out};
-  if (int rc = kkt_check(h, B, nr, a)) return rc;
-  const Params& P = h->hp;
-  const size_t nw = P.nwE, ng = P.ng, np = P.npE, nX = (size_t)P.nxE * (P.N + 1);
-  // staging: the eight inputs (absent ones take no room), the three outputs, then the verdicts
-  const double* src[8] = {x, p, lam_g, sigma_x, sigma_s, delta, r_w, r_g};
-  const int64_t ld[8] = {ld_x, ld_p, ld_lam_g, ld_sigma_x, ld_sigma_s, ld_delta, ld_r_w, ld_r_g};
-  const size_t vlen[8] = {nw, np, ng, nw, ng, 1, nw * (size_t)nr, ng * (size_t)nr};
-  double* hout[3] = {dw_out, dX_out, jdw_out};
-  const size_t olen[3] = {nw * (size_t)nr, nX * (size_t)nr, ng * (size_t)nr};
-  size_t n_in[8], total = 0;
-  for (int i = 0; i < 8; ++i) {
-    n_in[i] = !src[i] ? 0 : (ld[i] == 0 ? vlen[i] : (size_t)(B - 1) * (size_t)ld[i] + vlen[i]);
-    total += n_in[i];
-  }
-  for (int i = 0; i < 3; ++i) total += hout[i] ? (size_t)B * olen[i] : 0;
-  total += info_out ? ((size_t)B + 1) / 2 : 0;  // B int32 in whole doubles
-  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
-  double* q = h->dbuf;
-  const double* din[8];
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 8; ++i) {
-    din[i] = src[i] ? q : nullptr;
-    if (src[i] && e == hipSuccess) e = hipMemcpy(q, src[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
-    q += n_in[i];
-  }
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
-  double* dout[3];
-  for (int i = 0; i < 3; ++i) {
-    dout[i] = hout[i] ? q : nullptr;
-    q += hout[i] ? (size_t)B * olen[i] : 0;
-  }
-  int32_t* dinfo = info_out ? (int32_t*)q : nullptr;
-  const KktArgs d{din[0], din[1], din[2], din[3], din[4], din[5], din[6], din[7], ld_x, ld_p, ld_lam_g,
-                  ld_sigma_x, ld_sigma_s, ld_delta, ld_r_w, ld_r_g, obj_factor, dout[0], dout[1], dout[2], dinfo};
-  if (int rc = kkt_enqueue(h, B, nr, d, nullptr)) return rc;
-  e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
-  for (int i = 0; i < 3; ++i)
-    if (hout[i] && e == hipSuccess)
-      e = hipMemcpy(hout[i], dout[i], (size_t)B * olen[i] * sizeof(double), hipMemcpyDeviceToHost);
-  if (info_out && e == hipSuccess) e = hipMemcpy(info_out, dinfo, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
-  return NMPC_OK;
+  CallArgs a{{x, p, lam_g, sigma_x, sigma_s, delta, r_w, r_g},
+             {ld_x, ld_p, ld_lam_g, ld_sigma_x, ld_sigma_s, ld_delta, ld_r_w, ld_r_g}, 8,
+             {dw_out, dX_out, jdw_out}, 3, info_out, 1, nr, obj_factor};
+  if (int rc = kkt_check(h, B, a)) return rc;
+  return staged(h, B, a, kkt_launch, "KKT solve", kKktWs);
 }
 
 // ---- parameter-direction products at given points (kernel: nmpc_pproducts.hip)
-struct PprodArgs {
-  const double *x, *p, *lam_g, *dp;
-  int64_t ld_x, ld_p, ld_lam_g, ld_dp;
-  double obj_factor;
-  double *jp, *hp, *dXp, *gp;
-};
-// the argument checks of both entry points: nothing here touches the device
-static int pprod_check(const nmpc_handle* h, int32_t B, int32_t nd, const PprodArgs& a) {
-  if (!h) return fail(NMPC_E_INVALID, "null handle");
-  if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
-  if (nd < 0) return fail(NMPC_E_INVALID, "nd < 0");
-  if (!a.x || !a.p) return fail(NMPC_E_INVALID, "required pointer is null (x, p)");
-  if (!a.jp && !a.hp && !a.dXp && !a.gp) return fail(NMPC_E_INVALID, "every output pointer is null");
-  if (nd == 0 && (a.dp || a.jp || a.hp || a.dXp))
-    return fail(NMPC_E_INVALID, "nd = 0 takes gp_out alone (dp and the directional outputs must be null)");
-  if (nd > 0 && !a.dp) return fail(NMPC_E_INVALID, "required pointer is null (dp with nd > 0)");
-  const Params& P = h->hp;
-  auto bad = [](const double* q, int64_t ld, int64_t n) { return q && ld != 0 && ld < n; };
-  if (bad(a.x, a.ld_x, P.nwE) || bad(a.p, a.ld_p, P.npE) || bad(a.lam_g, a.ld_lam_g, P.ng) ||
-      bad(a.dp, a.ld_dp, (int64_t)P.npE * nd))
-    return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
-  return NMPC_OK;
+static int pprod_check(const nmpc_handle* h, int32_t B, CallArgs& a) {
+  const char* own = nullptr;
+  if (all_null(a.out, 4)) own = "every output pointer is null";
+  else if (a.n == 0 && (a.in[3] || !all_null(a.out, 3)))
+    own = "nd = 0 takes gp_out alone (dp and the directional outputs must be null)";
+  else if (a.n > 0 && !a.in[3]) own = "required pointer is null (dp with nd > 0)";
+  return check(h, B, a.n < 0 ? "nd < 0" : nullptr, a, 0x3, "required pointer is null (x, p)", own,
+               [](const Params& P, CallArgs& a) {
+                 const auto [nw, ng, np, nX, nd] = dims(P, a);
+                 set_lens(a.vlen, {nw, np, ng, np * nd});
+                 set_lens(a.olen, {ng * nd, nw * nd, nX * nd, np});
+               });
 }
-// checked arguments, DEVICE pointers: workspace and chunks as prod_enqueue, then one launch
-static int pprod_enqueue(nmpc_handle* h, int32_t B, int32_t nd, const PprodArgs& a, void* stream) {
-  const int per = h->ws_doubles > kPprodWs ? h->ws_doubles : kPprodWs;
-  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
-  const int chunks = prod_chunks(per, kPprodWs, B, nd);
+// workspace and chunks as prod_launch
+static int pprod_launch(const nmpc_handle* h, int32_t B, const CallArgs& a, void* stream) {
   PprodIO io;
-  io.x = a.x; io.p = a.p; io.lam_g = a.lam_g; io.dp = a.dp;
-  io.ld_x = a.ld_x; io.ld_p = a.ld_p; io.ld_lam_g = a.ld_lam_g; io.ld_dp = a.ld_dp;
-  io.obj_factor = a.obj_factor; io.nd = nd;
-  io.jp = a.jp; io.hp = a.hp; io.dXp = a.dXp; io.gp = a.gp;
+  io.x = a.in[0]; io.p = a.in[1]; io.lam_g = a.in[2]; io.dp = a.in[3];
+  io.ld_x = a.ld[0]; io.ld_p = a.ld[1]; io.ld_lam_g = a.ld[2]; io.ld_dp = a.ld[3];
+  io.obj_factor = a.obj_factor; io.nd = a.n;
+  io.jp = a.out[0]; io.hp = a.out[1]; io.dXp = a.out[2]; io.gp = a.out[3];
   io.ws = h->dws;
-  const hipError_t e = (hipError_t)nmpc_pproducts_launch(h->dprm, (int)B, chunks, io, stream);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("parameter products launch: ") + hipGetErrorString(e));
-  return NMPC_OK;
+  return nmpc_pproducts_launch(h->dprm, (int)B, prod_chunks(ws_per(h, kPprodWs), kPprodWs, B, a.n), io, stream);
 }
 
 int nmpc_param_products_batch_dev(nmpc_handle* h, int32_t B, int32_t nd, const double* x, int64_t ld_x,
                                   const double* p, int64_t ld_p, const double* lam_g, int64_t ld_lam_g,
                                   double obj_factor, const double* dp, int64_t ld_dp, double* jp_out, double* hp_out,
                                   double* dXp_out, double* gp_out, void* stream) {
-  const PprodArgs a{x, p, lam_g, dp, ld_x, ld_p, ld_lam_g, ld_dp, obj_factor, jp_out, hp_out, dXp_out, gp_out};
-  if (int rc = pprod_check(h, B, nd, a)) return rc;
-  return pprod_enqueue(h, B, nd, a, stream);
+  CallArgs a{{x, p, lam_g, dp}, {ld_x, ld_p, ld_lam_g, ld_dp}, 4, {jp_out, hp_out, dXp_out, gp_out}, 4, nullptr, 0,
+             nd, obj_factor};
+  if (int rc = pprod_check(h, B, a)) return rc;
+  return enqueue(h, B, a, stream, pprod_launch, "parameter products", kPprodWs);
 }
 
 int nmpc_param_products_batch(nmpc_handle* h, int32_t B, int32_t nd, const double* x, int64_t ld_x, const double* p,
                               int64_t ld_p, const double* lam_g, int64_t ld_lam_g, double obj_factor,
                               const double* dp, int64_t ld_dp, double* jp_out, double* hp_out, double* dXp_out,
                               double* gp_out) {
-  const PprodArgs a{x, p, lam_g, dp, ld_x, ld_p, ld_lam_g, ld_dp, obj_factor, jp_out, hp_out, dXp_out, gp_out};
-  if (int rc = pprod_check(h, B, nd, a)) return rc;
-  const Params& P = h->hp;
-  const size_t nw = P.nwE, ng = P.ng, np = P.npE, nX = (size_t)P.nxE * (P.N + 1);
-  // staging: the four inputs (absent ones take no room), then the four outputs
-  const double* src[4] = {x, p, lam_g, dp};
-  const int64_t ld[4] = {ld_x, ld_p, ld_lam_g, ld_dp};
-  const size_t vlen[4] = {nw, np, ng, np * (size_t)nd};
-  double* hout[4] = {jp_out, hp_out, dXp_out, gp_out};
-  const size_t olen[4] = {ng * (size_t)nd, nw * (size_t)nd, nX * (size_t)nd, np};
-  size_t n_in[4], total = 0;
-  for (int i = 0; i < 4; ++i) {
-    n_in[i] = !src[i] ? 0 : (ld[i] == 0 ? vlen[i] : (size_t)(B - 1) * (size_t)ld[i] + vlen[i]);
-    total += n_in[i];
-  }
-  for (int i = 0; i < 4; ++i) total += hout[i] ? (size_t)B * olen[i] : 0;
-  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
-  double* q = h->dbuf;
-  const double* din[4];
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 4; ++i) {
-    din[i] = src[i] ? q : nullptr;
-    if (src[i] && e == hipSuccess) e = hipMemcpy(q, src[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
-    q += n_in[i];
-  }
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
-  double* dout[4];
-  for (int i = 0; i < 4; ++i) {
-    dout[i] = hout[i] ? q : nullptr;
-    q += hout[i] ? (size_t)B * olen[i] : 0;
-  }
-  const PprodArgs d{din[0], din[1], din[2], din[3], ld_x, ld_p, ld_lam_g, ld_dp, obj_factor,
-                    dout[0], dout[1], dout[2], dout[3]};
-  if (int rc = pprod_enqueue(h, B, nd, d, nullptr)) return rc;
-  e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
-  for (int i = 0; i < 4; ++i)
-    if (hout[i] && e == hipSuccess)
-      e = hipMemcpy(hout[i], dout[i], (size_t)B * olen[i] * sizeof(double), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
-  return NMPC_OK;
+  CallArgs a{{x, p, lam_g, dp}, {ld_x, ld_p, ld_lam_g, ld_dp}, 4, {jp_out, hp_out, dXp_out, gp_out}, 4, nullptr, 0,
+             nd, obj_factor};
+  if (int rc = pprod_check(h, B, a)) return rc;
+  return staged(h, B, a, pprod_launch, "parameter products", kPprodWs);
 }
 
 // ---- adjoint (transposed) products at given points (kernel: nmpc_adjoint.hip)
-struct AdjArgs {
-  const double *x, *p, *lam_g, *y, *z, *Xb;
-  int64_t ld_x, ld_p, ld_lam_g, ld_y, ld_z, ld_Xb;
-  double obj_factor;
-  double *wbar, *pbar;
-};
-// the argument checks of both entry points: nothing here touches the device
-static int adj_check(const nmpc_handle* h, int32_t B, int32_t na, const AdjArgs& a) {
-  if (!h) return fail(NMPC_E_INVALID, "null handle");
-  if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
-  if (na <= 0) return fail(NMPC_E_INVALID, "na <= 0");
-  if (!a.x || !a.p) return fail(NMPC_E_INVALID, "required pointer is null (x, p)");
-  if (!a.y && !a.z && !a.Xb) return fail(NMPC_E_INVALID, "every seed pointer is null (y, z, Xb)");
-  if (!a.wbar && !a.pbar) return fail(NMPC_E_INVALID, "every output pointer is null (wbar, pbar)");
-  const Params& P = h->hp;
-  auto bad = [](const double* q, int64_t ld, int64_t n) { return q && ld != 0 && ld < n; };
-  if (bad(a.x, a.ld_x, P.nwE) || bad(a.p, a.ld_p, P.npE) || bad(a.lam_g, a.ld_lam_g, P.ng) ||
-      bad(a.y, a.ld_y, (int64_t)P.ng * na) || bad(a.z, a.ld_z, (int64_t)P.nwE * na) ||
-      bad(a.Xb, a.ld_Xb, (int64_t)P.nxE * (P.N + 1) * na))
-    return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
-  return NMPC_OK;
+static int adj_check(const nmpc_handle* h, int32_t B, CallArgs& a) {
+  const char* own = nullptr;
+  if (all_null(a.in + 3, 3)) own = "every seed pointer is null (y, z, Xb)";
+  else if (all_null(a.out, 2)) own = "every output pointer is null (wbar, pbar)";
+  return check(h, B, a.n <= 0 ? "na <= 0" : nullptr, a, 0x3, "required pointer is null (x, p)", own,
+               [](const Params& P, CallArgs& a) {
+                 const auto [nw, ng, np, nX, na] = dims(P, a);
+                 set_lens(a.vlen, {nw, np, ng, ng * na, nw * na, nX * na});
+                 set_lens(a.olen, {nw * na, np * na});
+               });
 }
-// checked arguments, DEVICE pointers: workspace and chunks as prod_enqueue, then one launch
-static int adj_enqueue(nmpc_handle* h, int32_t B, int32_t na, const AdjArgs& a, void* stream) {
-  const int per = h->ws_doubles > kAdjWs ? h->ws_doubles : kAdjWs;
-  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
-  const int chunks = prod_chunks(per, kAdjWs, B, na);
+// workspace and chunks as prod_launch
+static int adj_launch(const nmpc_handle* h, int32_t B, const CallArgs& a, void* stream) {
   AdjIO io;
-  io.x = a.x; io.p = a.p; io.lam_g = a.lam_g; io.y = a.y; io.z = a.z; io.Xb = a.Xb;
-  io.ld_x = a.ld_x; io.ld_p = a.ld_p; io.ld_lam_g = a.ld_lam_g; io.ld_y = a.ld_y; io.ld_z = a.ld_z;
-  io.ld_Xb = a.ld_Xb;
-  io.obj_factor = a.obj_factor; io.na = na;
-  io.wbar = a.wbar; io.pbar = a.pbar;
+  io.x = a.in[0]; io.p = a.in[1]; io.lam_g = a.in[2]; io.y = a.in[3]; io.z = a.in[4]; io.Xb = a.in[5];
+  io.ld_x = a.ld[0]; io.ld_p = a.ld[1]; io.ld_lam_g = a.ld[2]; io.ld_y = a.ld[3]; io.ld_z = a.ld[4];
+  io.ld_Xb = a.ld[5];
+  io.obj_factor = a.obj_factor; io.na = a.n;
+  io.wbar = a.out[0]; io.pbar = a.out[1];
   io.ws = h->dws;
-  const hipError_t e = (hipError_t)nmpc_adjoint_launch(h->dprm, (int)B, chunks, io, stream);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("adjoint products launch: ") + hipGetErrorString(e));
-  return NMPC_OK;
+  return nmpc_adjoint_launch(h->dprm, (int)B, prod_chunks(ws_per(h, kAdjWs), kAdjWs, B, a.n), io, stream);
 }
 
 int nmpc_adjoint_products_batch_dev(nmpc_handle* h, int32_t B, int32_t na, const double* x, int64_t ld_x,
@@ -6097,172 +5971,59 @@ int nmpc_adjoint_products_batch_dev(nmpc_handle* h, int32_t B, int32_t na, const
                                     double obj_factor, const double* y, int64_t ld_y, const double* z, int64_t ld_z,
                                     const double* Xb, int64_t ld_Xb, double* wbar_out, double* pbar_out,
                                     void* stream) {
-  const AdjArgs a{x, p, lam_g, y, z, Xb, ld_x, ld_p, ld_lam_g, ld_y, ld_z, ld_Xb, obj_factor, wbar_out, pbar_out};
-  if (int rc = adj_check(h, B, na, a)) return rc;
-  return adj_enqueue(h, B, na, a, stream);
+  CallArgs a{{x, p, lam_g, y, z, Xb}, {ld_x, ld_p, ld_lam_g, ld_y, ld_z, ld_Xb}, 6, {wbar_out, pbar_out}, 2, nullptr,
+             0, na, obj_factor};
+  if (int rc = adj_check(h, B, a)) return rc;
+  return enqueue(h, B, a, stream, adj_launch, "adjoint products", kAdjWs);
 }
 
 int nmpc_adjoint_products_batch(nmpc_handle* h, int32_t B, int32_t na, const double* x, int64_t ld_x,
                                 const double* p, int64_t ld_p, const double* lam_g, int64_t ld_lam_g,
                                 double obj_factor, const double* y, int64_t ld_y, const double* z, int64_t ld_z,
                                 const double* Xb, int64_t ld_Xb, double* wbar_out, double* pbar_out) {
-  const AdjArgs a{x, p, lam_g, y, z, Xb, ld_x, ld_p, ld_lam_g, ld_y, ld_z, ld_Xb, obj_factor, wbar_out, pbar_out};
-  if (int rc = adj_check(h, B, na, a)) return rc;
-  const Params& P = h->hp;
-  const size_t nw = P.nwE, ng = P.ng, np = P.npE, nX = (size_t)P.nxE * (P.N + 1);
-  // staging: the six inputs (absent ones take no room), then the two outputs
-  const double* src[6] = {x, p, lam_g, y, z, Xb};
-  const int64_t ld[6] = {ld_x, ld_p, ld_lam_g, ld_y, ld_z, ld_Xb};
-  const size_t vlen[6] = {nw, np, ng, ng * (size_t)na, nw * (size_t)na, nX * (size_t)na};
-  double* hout[2] = {wbar_out, pbar_out};
-  const size_t olen[2] = {nw * (size_t)na, np * (size_t)na};
-  size_t n_in[6], total = 0;
-  for (int i = 0; i < 6; ++i) {
-    n_in[i] = !src[i] ? 0 : (ld[i] == 0 ? vlen[i] : (size_t)(B - 1) * (size_t)ld[i] + vlen[i]);
-    total += n_in[i];
-  }
-  for (int i = 0; i < 2; ++i) total += hout[i] ? (size_t)B * olen[i] : 0;
-  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
-  double* q = h->dbuf;
-  const double* din[6];
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 6; ++i) {
-    din[i] = src[i] ? q : nullptr;
-    if (src[i] && e == hipSuccess) e = hipMemcpy(q, src[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
-    q += n_in[i];
-  }
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
-  double* dout[2];
-  for (int i = 0; i < 2; ++i) {
-    dout[i] = hout[i] ? q : nullptr;
-    q += hout[i] ? (size_t)B * olen[i] : 0;
-  }
-  const AdjArgs d{din[0], din[1], din[2], din[3], din[4], din[5], ld_x, ld_p, ld_lam_g, ld_y, ld_z, ld_Xb,
-                  obj_factor, dout[0], dout[1]};
-  if (int rc = adj_enqueue(h, B, na, d, nullptr)) return rc;
-  e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
-  for (int i = 0; i < 2; ++i)
-    if (hout[i] && e == hipSuccess)
-      e = hipMemcpy(hout[i], dout[i], (size_t)B * olen[i] * sizeof(double), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
-  return NMPC_OK;
+  CallArgs a{{x, p, lam_g, y, z, Xb}, {ld_x, ld_p, ld_lam_g, ld_y, ld_z, ld_Xb}, 6, {wbar_out, pbar_out}, 2, nullptr,
+             0, na, obj_factor};
+  if (int rc = adj_check(h, B, a)) return rc;
+  return staged(h, B, a, adj_launch, "adjoint products", kAdjWs);
 }
 
 // ---- the kernels at a solve's point (x*, lam_g*, lam_x*): the reverse-mode sensitivity
 // (nmpc_solve_adjoint.hip), the forward-mode sensitivity (nmpc_solve_tangent.hip) and the feedback
-// policy (nmpc_solve_policy.hip).  One argument block, one check, one enqueue and one staging
-// routine serve the three entry-point pairs
-struct PointArgs {
-  // x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, then the entry point's own inputs
-  const double* in[12];
-  int64_t ld[12];
-  int nin;
-  // the entry point's double outputs, delta last
-  double* out[6];
-  int nout;
-  int32_t* info;
-  int32_t n;  // seeds or directions
-  // filled by point_check: the vector length each input's leading dimension must cover, and the
-  // per-scenario length of each output
-  size_t vlen[12], olen[6];
-};
-// fills the entry point's IO block from checked arguments (DEVICE pointers) and launches
-typedef int (*PointLaunch)(const nmpc_handle* h, int32_t B, const PointArgs& a, void* stream);
-
-// the argument checks of an entry-point pair, in the order of their messages: nothing here
-// touches the device.  count_err and own_err are the entry point's own rules (null: met);
-// inputs 0 .. nreq - 1 are required apart from g; own_lengths fills vlen from 9 on and olen
-static int point_check(const nmpc_handle* h, int32_t B, const char* count_err, PointArgs& a, int nreq,
-                       const char* req_err, const char* own_err, void (*own_lengths)(const Params&, PointArgs&)) {
-  if (!h) return fail(NMPC_E_INVALID, "null handle");
-  if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
-  if (count_err) return fail(NMPC_E_INVALID, count_err);
-  for (int i = 0; i < nreq; ++i)
-    if (i != 4 && !a.in[i]) return fail(NMPC_E_INVALID, req_err);
-  if (own_err) return fail(NMPC_E_INVALID, own_err);
-  const Params& P = h->hp;
-  const size_t nw = P.nwE, ng = P.ng, np = P.npE;
-  const size_t v[9] = {nw, np, ng, nw, ng, nw, nw, ng, ng};
-  for (int i = 0; i < 9; ++i) a.vlen[i] = v[i];
-  own_lengths(P, a);
-  for (int i = 0; i < a.nin; ++i)
-    if (a.in[i] && a.ld[i] != 0 && a.ld[i] < (int64_t)a.vlen[i])
-      return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
-  return NMPC_OK;
+// policy (nmpc_solve_policy.hip).  Inputs x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, then the
+// entry point's own; of the nine all but g are required; delta is the last output
+static const unsigned kPointReq = 0x1ef;
+static void point_lengths(const Params& P, CallArgs& a) {
+  const auto [nw, ng, np, nX, n] = dims(P, a);
+  set_lens(a.vlen, {nw, np, ng, nw, ng, nw, nw, ng, ng});
 }
 // the kernels' common argument block
-static PointIO point_io(const nmpc_handle* h, const PointArgs& a) {
+static PointIO point_io(const nmpc_handle* h, const CallArgs& a) {
   PointIO io;
   io.x = a.in[0]; io.p = a.in[1]; io.lam_g = a.in[2]; io.lam_x = a.in[3]; io.g = a.in[4];
   io.lbx = a.in[5]; io.ubx = a.in[6]; io.lbg = a.in[7]; io.ubg = a.in[8];
   io.ld_x = a.ld[0]; io.ld_p = a.ld[1]; io.ld_lam_g = a.ld[2]; io.ld_lam_x = a.ld[3]; io.ld_g = a.ld[4];
   io.ld_lbx = a.ld[5]; io.ld_ubx = a.ld[6]; io.ld_lbg = a.ld[7]; io.ld_ubg = a.ld[8];
-  io.info = a.info; io.delta = a.out[a.nout - 1];
+  io.info = a.iout; io.delta = a.out[a.nout - 1];
   io.ws = h->dws;
   return io;
-}
-// checked arguments, DEVICE pointers: workspace from the handle (sized like a solve's, grown
-// only when it does not cover B yet), then one launch
-static int point_enqueue(nmpc_handle* h, int32_t B, const PointArgs& a, void* stream, PointLaunch launch,
-                         const char* what) {
-  const int per = h->ws_doubles > kPointWs ? h->ws_doubles : kPointWs;
-  if (int rc = ensure_buf(&h->dws, &h->ws_bytes, (size_t)B * per * sizeof(double), "workspace")) return rc;
-  const hipError_t e = (hipError_t)launch(h, B, a, stream);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
-  return NMPC_OK;
-}
-// checked arguments, HOST pointers.  Staging: the inputs (absent ones take no room), the
-// outputs, the verdicts; H2D, one launch, sync, D2H
-static int point_staged(nmpc_handle* h, int32_t B, const PointArgs& a, PointLaunch launch, const char* what) {
-  size_t n_in[12], total = 0;
-  for (int i = 0; i < a.nin; ++i) {
-    n_in[i] = !a.in[i] ? 0 : (a.ld[i] == 0 ? a.vlen[i] : (size_t)(B - 1) * (size_t)a.ld[i] + a.vlen[i]);
-    total += n_in[i];
-  }
-  for (int i = 0; i < a.nout; ++i) total += a.out[i] ? (size_t)B * a.olen[i] : 0;
-  total += a.info ? ((size_t)B + 1) / 2 : 0;  // B int32 in whole doubles
-  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
-  double* q = h->dbuf;
-  PointArgs d = a;
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < a.nin; ++i) {
-    d.in[i] = a.in[i] ? q : nullptr;
-    if (a.in[i] && e == hipSuccess) e = hipMemcpy(q, a.in[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
-    q += n_in[i];
-  }
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
-  for (int i = 0; i < a.nout; ++i) {
-    d.out[i] = a.out[i] ? q : nullptr;
-    q += a.out[i] ? (size_t)B * a.olen[i] : 0;
-  }
-  d.info = a.info ? (int32_t*)q : nullptr;
-  if (int rc = point_enqueue(h, B, d, nullptr, launch, what)) return rc;
-  e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
-  for (int i = 0; i < a.nout; ++i)
-    if (a.out[i] && e == hipSuccess)
-      e = hipMemcpy(a.out[i], d.out[i], (size_t)B * a.olen[i] * sizeof(double), hipMemcpyDeviceToHost);
-  if (a.info && e == hipSuccess) e = hipMemcpy(a.info, d.info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
-  return NMPC_OK;
 }
 
 // ---- reverse-mode sensitivity of a solution in one launch (kernel: nmpc_solve_adjoint.hip)
 // own inputs x_bar, lam_g_bar, X_bar; outputs pbar, q, jq, delta
-static int sadj_check(const nmpc_handle* h, int32_t B, PointArgs& a) {
+static int sadj_check(const nmpc_handle* h, int32_t B, CallArgs& a) {
   const char* own = nullptr;
-  if (!a.in[9] && !a.in[10] && !a.in[11]) own = "every seed pointer is null (x_bar, lam_g_bar, X_bar)";
-  else if (!a.out[0] && !a.out[1]) own = "both pbar_out and q_out are null";
-  return point_check(h, B, a.n <= 0 ? "na <= 0" : nullptr, a, 9,
-                     "required pointer is null (x, p, lam_g, lam_x, lbx, ubx, lbg, ubg)", own,
-                     [](const Params& P, PointArgs& a) {
-                       const size_t nw = P.nwE, ng = P.ng, np = P.npE, nX = (size_t)P.nxE * (P.N + 1), na = a.n;
-                       a.vlen[9] = nw * na; a.vlen[10] = ng * na; a.vlen[11] = nX * na;
-                       a.olen[0] = np * na; a.olen[1] = nw * na; a.olen[2] = ng * na; a.olen[3] = 1;
-                     });
+  if (all_null(a.in + 9, 3)) own = "every seed pointer is null (x_bar, lam_g_bar, X_bar)";
+  else if (all_null(a.out, 2)) own = "both pbar_out and q_out are null";
+  return check(h, B, a.n <= 0 ? "na <= 0" : nullptr, a, kPointReq,
+               "required pointer is null (x, p, lam_g, lam_x, lbx, ubx, lbg, ubg)", own,
+               [](const Params& P, CallArgs& a) {
+                 const auto [nw, ng, np, nX, na] = dims(P, a);
+                 point_lengths(P, a);
+                 set_lens(a.vlen + 9, {nw * na, ng * na, nX * na});
+                 set_lens(a.olen, {np * na, nw * na, ng * na, 1});
+               });
 }
-static int sadj_launch(const nmpc_handle* h, int32_t B, const PointArgs& a, void* stream) {
+static int sadj_launch(const nmpc_handle* h, int32_t B, const CallArgs& a, void* stream) {
   SadjIO io;
   io.pt = point_io(h, a);
   io.x_bar = a.in[9]; io.lam_g_bar = a.in[10]; io.X_bar = a.in[11];
@@ -6280,12 +6041,12 @@ int nmpc_solve_adjoint_batch_dev(nmpc_handle* h, int32_t B, int32_t na, const do
                                  const double* x_bar, int64_t ld_x_bar, const double* lam_g_bar,
                                  int64_t ld_lam_g_bar, const double* X_bar, int64_t ld_X_bar, double* pbar_out,
                                  double* q_out, double* jq_out, int32_t* info_out, double* delta_out, void* stream) {
-  PointArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, x_bar, lam_g_bar, X_bar},
-              {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_x_bar, ld_lam_g_bar,
-               ld_X_bar},
-              12, {pbar_out, q_out, jq_out, delta_out}, 4, info_out, na};
+  CallArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, x_bar, lam_g_bar, X_bar},
+             {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_x_bar, ld_lam_g_bar,
+              ld_X_bar},
+             12, {pbar_out, q_out, jq_out, delta_out}, 4, info_out, 1, na};
   if (int rc = sadj_check(h, B, a)) return rc;
-  return point_enqueue(h, B, a, stream, sadj_launch, "solve adjoint");
+  return enqueue(h, B, a, stream, sadj_launch, "solve adjoint", kPointWs);
 }
 
 int nmpc_solve_adjoint_batch(nmpc_handle* h, int32_t B, int32_t na, const double* x, int64_t ld_x, const double* p,
@@ -6296,30 +6057,28 @@ int nmpc_solve_adjoint_batch(nmpc_handle* h, int32_t B, int32_t na, const double
                              const double* lam_g_bar, int64_t ld_lam_g_bar, const double* X_bar, int64_t ld_X_bar,
                              double* pbar_out, double* q_out, double* jq_out, int32_t* info_out,
                              double* delta_out) {
-  PointArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, x_bar, lam_g_bar, X_bar},
-              {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_x_bar, ld_lam_g_bar,
-               ld_X_bar},
-              12, {pbar_out, q_out, jq_out, delta_out}, 4, info_out, na};
+  CallArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, x_bar, lam_g_bar, X_bar},
+             {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_x_bar, ld_lam_g_bar,
+              ld_X_bar},
+             12, {pbar_out, q_out, jq_out, delta_out}, 4, info_out, 1, na};
   if (int rc = sadj_check(h, B, a)) return rc;
-  return point_staged(h, B, a, sadj_launch, "solve adjoint");
+  return staged(h, B, a, sadj_launch, "solve adjoint", kPointWs);
 }
 
-// ---- forward-mode sensitivity of a solution in one launch (kernel: nmpc_solve_tangent.hip) and
-// the plan's feedback policy in one launch (kernel: nmpc_solve_policy.hip): own input dp
-static void dp_length(const Params& P, PointArgs& a) { a.vlen[9] = (size_t)P.npE * (size_t)a.n; }
-// outputs dx, dlam_g, dX, delta
-static int stan_check(const nmpc_handle* h, int32_t B, PointArgs& a) {
-  return point_check(h, B, a.n <= 0 ? "nd <= 0" : nullptr, a, 10,
-                     "required pointer is null (x, p, lam_g, lam_x, lbx, ubx, lbg, ubg, dp)",
-                     !a.out[0] && !a.out[1] && !a.out[2] ? "dx_out, dlam_g_out and dX_out are all null" : nullptr,
-                     [](const Params& P, PointArgs& a) {
-                       const size_t nd = a.n;
-                       dp_length(P, a);
-                       a.olen[0] = P.nwE * nd; a.olen[1] = P.ng * nd; a.olen[2] = (size_t)P.nxE * (P.N + 1) * nd;
-                       a.olen[3] = 1;
-                     });
+// ---- forward-mode sensitivity of a solution in one launch (kernel: nmpc_solve_tangent.hip):
+// own input dp, required; outputs dx, dlam_g, dX, delta
+static int stan_check(const nmpc_handle* h, int32_t B, CallArgs& a) {
+  return check(h, B, a.n <= 0 ? "nd <= 0" : nullptr, a, kPointReq | 0x200,
+               "required pointer is null (x, p, lam_g, lam_x, lbx, ubx, lbg, ubg, dp)",
+               all_null(a.out, 3) ? "dx_out, dlam_g_out and dX_out are all null" : nullptr,
+               [](const Params& P, CallArgs& a) {
+                 const auto [nw, ng, np, nX, nd] = dims(P, a);
+                 point_lengths(P, a);
+                 a.vlen[9] = np * nd;
+                 set_lens(a.olen, {nw * nd, ng * nd, nX * nd, 1});
+               });
 }
-static int stan_launch(const nmpc_handle* h, int32_t B, const PointArgs& a, void* stream) {
+static int stan_launch(const nmpc_handle* h, int32_t B, const CallArgs& a, void* stream) {
   StanIO io;
   io.pt = point_io(h, a);
   io.dp = a.in[9]; io.ld_dp = a.ld[9]; io.nd = a.n;
@@ -6334,11 +6093,11 @@ int nmpc_solve_tangent_batch_dev(nmpc_handle* h, int32_t B, int32_t nd, const do
                                  const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg,
                                  const double* dp, int64_t ld_dp, double* dx_out, double* dlam_g_out,
                                  double* dX_out, int32_t* info_out, double* delta_out, void* stream) {
-  PointArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
-              {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp}, 10,
-              {dx_out, dlam_g_out, dX_out, delta_out}, 4, info_out, nd};
+  CallArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
+             {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp}, 10,
+             {dx_out, dlam_g_out, dX_out, delta_out}, 4, info_out, 1, nd};
   if (int rc = stan_check(h, B, a)) return rc;
-  return point_enqueue(h, B, a, stream, stan_launch, "solve tangent");
+  return enqueue(h, B, a, stream, stan_launch, "solve tangent", kPointWs);
 }
 
 int nmpc_solve_tangent_batch(nmpc_handle* h, int32_t B, int32_t nd, const double* x, int64_t ld_x, const double* p,
@@ -6347,29 +6106,30 @@ int nmpc_solve_tangent_batch(nmpc_handle* h, int32_t B, int32_t nd, const double
                              const double* ubx, int64_t ld_ubx, const double* lbg, int64_t ld_lbg,
                              const double* ubg, int64_t ld_ubg, const double* dp, int64_t ld_dp, double* dx_out,
                              double* dlam_g_out, double* dX_out, int32_t* info_out, double* delta_out) {
-  PointArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
-              {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp}, 10,
-              {dx_out, dlam_g_out, dX_out, delta_out}, 4, info_out, nd};
+  CallArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
+             {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp}, 10,
+             {dx_out, dlam_g_out, dX_out, delta_out}, 4, info_out, 1, nd};
   if (int rc = stan_check(h, B, a)) return rc;
-  return point_staged(h, B, a, stan_launch, "solve tangent");
+  return staged(h, B, a, stan_launch, "solve tangent", kPointWs);
 }
 
+// ---- the plan's feedback policy in one launch (kernel: nmpc_solve_policy.hip): own input dp;
 // outputs K, kff, A, B, X, delta
-static int spol_check(const nmpc_handle* h, int32_t B, PointArgs& a) {
+static int spol_check(const nmpc_handle* h, int32_t B, CallArgs& a) {
   const char* own = nullptr;
   if (a.n > 0 && !a.in[9]) own = "dp is null with nd > 0";
   else if (a.n == 0 && (a.in[9] || a.out[1])) own = "dp and kff_out must be null with nd = 0";
-  else if (!a.out[0] && !a.out[1] && !a.out[2] && !a.out[3]) own = "K_out, kff_out, A_out and B_out are all null";
-  return point_check(h, B, a.n < 0 ? "nd < 0" : nullptr, a, 9,
-                     "required pointer is null (x, p, lam_g, lam_x, lbx, ubx, lbg, ubg)", own,
-                     [](const Params& P, PointArgs& a) {
-                       const size_t nu = P.nuE, nx = P.nxE, N = P.N;
-                       dp_length(P, a);
-                       a.olen[0] = nu * nx * N; a.olen[1] = (size_t)P.nwE * (size_t)a.n; a.olen[2] = nx * nx * N;
-                       a.olen[3] = nx * nu * N; a.olen[4] = nx * (N + 1); a.olen[5] = 1;
-                     });
+  else if (all_null(a.out, 4)) own = "K_out, kff_out, A_out and B_out are all null";
+  return check(h, B, a.n < 0 ? "nd < 0" : nullptr, a, kPointReq,
+               "required pointer is null (x, p, lam_g, lam_x, lbx, ubx, lbg, ubg)", own,
+               [](const Params& P, CallArgs& a) {
+                 const size_t nu = P.nuE, nx = P.nxE, N = P.N, nd = a.n;
+                 point_lengths(P, a);
+                 a.vlen[9] = (size_t)P.npE * nd;
+                 set_lens(a.olen, {nu * nx * N, (size_t)P.nwE * nd, nx * nx * N, nx * nu * N, nx * (N + 1), 1});
+               });
 }
-static int spol_launch(const nmpc_handle* h, int32_t B, const PointArgs& a, void* stream) {
+static int spol_launch(const nmpc_handle* h, int32_t B, const CallArgs& a, void* stream) {
   SpolIO io;
   io.pt = point_io(h, a);
   io.dp = a.in[9]; io.ld_dp = a.ld[9]; io.nd = a.n;
@@ -6384,11 +6144,11 @@ int nmpc_solve_policy_batch_dev(nmpc_handle* h, int32_t B, int32_t nd, const dou
                                 const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg,
                                 const double* dp, int64_t ld_dp, double* K_out, double* kff_out, double* A_out,
                                 double* B_out, double* X_out, int32_t* info_out, double* delta_out, void* stream) {
-  PointArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
-              {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp}, 10,
-              {K_out, kff_out, A_out, B_out, X_out, delta_out}, 6, info_out, nd};
+  CallArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
+             {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp}, 10,
+             {K_out, kff_out, A_out, B_out, X_out, delta_out}, 6, info_out, 1, nd};
   if (int rc = spol_check(h, B, a)) return rc;
-  return point_enqueue(h, B, a, stream, spol_launch, "solve policy");
+  return enqueue(h, B, a, stream, spol_launch, "solve policy", kPointWs);
 }
 
 int nmpc_solve_policy_batch(nmpc_handle* h, int32_t B, int32_t nd, const double* x, int64_t ld_x, const double* p,
@@ -6398,58 +6158,38 @@ int nmpc_solve_policy_batch(nmpc_handle* h, int32_t B, int32_t nd, const double*
                             const double* ubg, int64_t ld_ubg, const double* dp, int64_t ld_dp, double* K_out,
                             double* kff_out, double* A_out, double* B_out, double* X_out, int32_t* info_out,
                             double* delta_out) {
-  PointArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
-              {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp}, 10,
-              {K_out, kff_out, A_out, B_out, X_out, delta_out}, 6, info_out, nd};
+  CallArgs a{{x, p, lam_g, lam_x, g, lbx, ubx, lbg, ubg, dp},
+             {ld_x, ld_p, ld_lam_g, ld_lam_x, ld_g, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_dp}, 10,
+             {K_out, kff_out, A_out, B_out, X_out, delta_out}, 6, info_out, 1, nd};
   if (int rc = spol_check(h, B, a)) return rc;
-  return point_staged(h, B, a, spol_launch, "solve policy");
+  return staged(h, B, a, spol_launch, "solve policy", kPointWs);
 }
 
-// ---- disturbance rollouts of the plan's feedback policy (kernel: nmpc_policy_rollout.hip)
-struct RollArgs {
-  // p, ubar, Xbar, K, lbx, ubx, lbg, ubg, e0, w
-  const double* in[10];
-  int64_t ld[10];
-  // J, viol, X, U
-  double* out[4];
-  int32_t* nsat;
-  // filled by roll_check: the vector length each input's leading dimension must cover, and the
-  // per-scenario length of each double output
-  size_t vlen[10], olen[4];
-};
-// the argument checks of both entry points: nothing here touches the device
-static int roll_check(const nmpc_handle* h, int32_t B, int32_t M, RollArgs& a) {
-  if (!h) return fail(NMPC_E_INVALID, "null handle");
-  if (B <= 0) return fail(NMPC_E_INVALID, "B <= 0");
-  if (M <= 0) return fail(NMPC_E_INVALID, "M <= 0");
-  if ((M + WAVE - 1) / WAVE > 65535) return fail(NMPC_E_INVALID, "M > 64 x 65535");
-  if (!a.in[0] || !a.in[1] || !a.in[2] || !a.in[8])
-    return fail(NMPC_E_INVALID, "required pointer is null (p, ubar, Xbar, e0)");
-  if (!a.out[0] && !a.out[1] && !a.out[2] && !a.out[3])
-    return fail(NMPC_E_INVALID, "J_out, viol_out, X_out and U_out are all null");
-  if (!a.in[6] != !a.in[7]) return fail(NMPC_E_INVALID, "lbg and ubg must be given together");
-  const Params& P = h->hp;
-  const size_t nw = P.nwE, nx = P.nxE, nu = P.nuE, N = P.N, ng = P.ng, nX = nx * (N + 1), m = M;
-  const size_t v[10] = {(size_t)P.npE, nw, nX, nu * nx * N, nw, nw, ng, ng, nx * m, nx * N * m};
-  for (int i = 0; i < 10; ++i) {
-    a.vlen[i] = v[i];
-    if (a.in[i] && a.ld[i] != 0 && a.ld[i] < (int64_t)v[i])
-      return fail(NMPC_E_INVALID, "leading dimension smaller than the vector length");
-  }
-  a.olen[0] = m; a.olen[1] = m; a.olen[2] = nX * m; a.olen[3] = nw * m;
-  return NMPC_OK;
+// ---- disturbance rollouts of the plan's feedback policy (kernel: nmpc_policy_rollout.hip):
+// inputs p, ubar, Xbar, K, lbx, ubx, lbg, ubg, e0, w; outputs J, viol, X, U and the M counts nsat
+static int roll_check(const nmpc_handle* h, int32_t B, CallArgs& a) {
+  const char* count = nullptr;
+  if (a.n <= 0) count = "M <= 0";
+  else if ((a.n + WAVE - 1) / WAVE > 65535) count = "M > 64 x 65535";
+  const char* own = nullptr;
+  if (all_null(a.out, 4)) own = "J_out, viol_out, X_out and U_out are all null";
+  else if (!a.in[6] != !a.in[7]) own = "lbg and ubg must be given together";
+  return check(h, B, count, a, 0x107, "required pointer is null (p, ubar, Xbar, e0)", own,
+               [](const Params& P, CallArgs& a) {
+                 const size_t nw = P.nwE, nx = P.nxE, nu = P.nuE, N = P.N, ng = P.ng, nX = nx * (N + 1), m = a.n;
+                 set_lens(a.vlen, {(size_t)P.npE, nw, nX, nu * nx * N, nw, nw, ng, ng, nx * m, nx * N * m});
+                 set_lens(a.olen, {m, m, nX * m, nw * m});
+                 a.ilen = m;
+               });
 }
-// checked arguments, DEVICE pointers: one launch, no workspace
-static int roll_enqueue(const nmpc_handle* h, int32_t B, int32_t M, const RollArgs& a, void* stream) {
+static int roll_launch(const nmpc_handle* h, int32_t B, const CallArgs& a, void* stream) {
   RollIO io;
   io.p = a.in[0]; io.ubar = a.in[1]; io.Xbar = a.in[2]; io.K = a.in[3]; io.lbx = a.in[4]; io.ubx = a.in[5];
   io.lbg = a.in[6]; io.ubg = a.in[7]; io.e0 = a.in[8]; io.w = a.in[9];
   io.ld_p = a.ld[0]; io.ld_ubar = a.ld[1]; io.ld_Xbar = a.ld[2]; io.ld_K = a.ld[3]; io.ld_lbx = a.ld[4];
   io.ld_ubx = a.ld[5]; io.ld_lbg = a.ld[6]; io.ld_ubg = a.ld[7]; io.ld_e0 = a.ld[8]; io.ld_w = a.ld[9];
-  io.J = a.out[0]; io.viol = a.out[1]; io.nsat = a.nsat; io.X = a.out[2]; io.U = a.out[3];
-  const hipError_t e = (hipError_t)nmpc_policy_rollout_launch(h->dprm, (int)B, (int)M, io, stream);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("policy rollout launch: ") + hipGetErrorString(e));
-  return NMPC_OK;
+  io.J = a.out[0]; io.viol = a.out[1]; io.nsat = a.iout; io.X = a.out[2]; io.U = a.out[3];
+  return nmpc_policy_rollout_launch(h->dprm, (int)B, (int)a.n, io, stream);
 }
 
 int nmpc_policy_rollout_batch_dev(nmpc_handle* h, int32_t B, int32_t M, const double* p, int64_t ld_p,
@@ -6459,11 +6199,11 @@ int nmpc_policy_rollout_batch_dev(nmpc_handle* h, int32_t B, int32_t M, const do
                                   const double* ubg, int64_t ld_ubg, const double* e0, int64_t ld_e0,
                                   const double* w, int64_t ld_w, double* J_out, double* viol_out, int32_t* nsat_out,
                                   double* X_out, double* U_out, void* stream) {
-  RollArgs a{{p, ubar, Xbar, K, lbx, ubx, lbg, ubg, e0, w},
-             {ld_p, ld_ubar, ld_Xbar, ld_K, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_e0, ld_w},
-             {J_out, viol_out, X_out, U_out}, nsat_out};
-  if (int rc = roll_check(h, B, M, a)) return rc;
-  return roll_enqueue(h, B, M, a, stream);
+  CallArgs a{{p, ubar, Xbar, K, lbx, ubx, lbg, ubg, e0, w},
+             {ld_p, ld_ubar, ld_Xbar, ld_K, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_e0, ld_w}, 10,
+             {J_out, viol_out, X_out, U_out}, 4, nsat_out, 0, M};
+  if (int rc = roll_check(h, B, a)) return rc;
+  return enqueue(h, B, a, stream, roll_launch, "policy rollout", 0);
 }
 
 int nmpc_policy_rollout_batch(nmpc_handle* h, int32_t B, int32_t M, const double* p, int64_t ld_p, const double* ubar,
@@ -6472,44 +6212,11 @@ int nmpc_policy_rollout_batch(nmpc_handle* h, int32_t B, int32_t M, const double
                               const double* lbg, int64_t ld_lbg, const double* ubg, int64_t ld_ubg, const double* e0,
                               int64_t ld_e0, const double* w, int64_t ld_w, double* J_out, double* viol_out,
                               int32_t* nsat_out, double* X_out, double* U_out) {
-  RollArgs a{{p, ubar, Xbar, K, lbx, ubx, lbg, ubg, e0, w},
-             {ld_p, ld_ubar, ld_Xbar, ld_K, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_e0, ld_w},
-             {J_out, viol_out, X_out, U_out}, nsat_out};
-  if (int rc = roll_check(h, B, M, a)) return rc;
-  // staging: the inputs (absent ones take no room), the outputs, the counts; H2D, one launch,
-  // sync, D2H
-  size_t n_in[10], total = 0;
-  for (int i = 0; i < 10; ++i) {
-    n_in[i] = !a.in[i] ? 0 : (a.ld[i] == 0 ? a.vlen[i] : (size_t)(B - 1) * (size_t)a.ld[i] + a.vlen[i]);
-    total += n_in[i];
-  }
-  for (int i = 0; i < 4; ++i) total += a.out[i] ? (size_t)B * a.olen[i] : 0;
-  total += a.nsat ? ((size_t)B * (size_t)M + 1) / 2 : 0;  // B M int32 in whole doubles
-  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * sizeof(double), "staging")) return rc;
-  double* q = h->dbuf;
-  RollArgs d = a;
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 10; ++i) {
-    d.in[i] = a.in[i] ? q : nullptr;
-    if (a.in[i] && e == hipSuccess) e = hipMemcpy(q, a.in[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice);
-    q += n_in[i];
-  }
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
-  for (int i = 0; i < 4; ++i) {
-    d.out[i] = a.out[i] ? q : nullptr;
-    q += a.out[i] ? (size_t)B * a.olen[i] : 0;
-  }
-  d.nsat = a.nsat ? (int32_t*)q : nullptr;
-  if (int rc = roll_enqueue(h, B, M, d, nullptr)) return rc;
-  e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("kernel: ") + hipGetErrorString(e));
-  for (int i = 0; i < 4; ++i)
-    if (a.out[i] && e == hipSuccess)
-      e = hipMemcpy(a.out[i], d.out[i], (size_t)B * a.olen[i] * sizeof(double), hipMemcpyDeviceToHost);
-  if (a.nsat && e == hipSuccess)
-    e = hipMemcpy(a.nsat, d.nsat, (size_t)B * (size_t)M * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(NMPC_E_HIP, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
-  return NMPC_OK;
+  CallArgs a{{p, ubar, Xbar, K, lbx, ubx, lbg, ubg, e0, w},
+             {ld_p, ld_ubar, ld_Xbar, ld_K, ld_lbx, ld_ubx, ld_lbg, ld_ubg, ld_e0, ld_w}, 10,
+             {J_out, viol_out, X_out, U_out}, 4, nsat_out, 0, M};
+  if (int rc = roll_check(h, B, a)) return rc;
+  return staged(h, B, a, roll_launch, "policy rollout", 0);
 }
 
 int nmpc_shift_dev(nmpc_handle* h, int32_t B, double* p, int64_t ld_p, const double* u_sol, double* w_out,

@@ -46,6 +46,62 @@ def _dptr(a: np.ndarray):
     return a.ctypes.data_as(_DP)
 
 
+def _flat_ins(ins):
+    """``[(array, ld)]`` (an absent one ``(None, 0)``) as the flat ``[pointer, ld, ...]``."""
+    flat = []
+    for a, ld in ins:
+        flat += [_dptr(a) if a is not None else None, ld]
+    return flat
+
+
+def _dev_in(t, tail, B, name):
+    """``[pointer, ld]`` of a device input: a float64 CUDA tensor of shape (B, *tail), or one the
+    batch shares, of shape tail (ld = 0); None gives the null pointer."""
+    import torch  # plumbing only: device memory and streams
+
+    if t is None:
+        return [C.c_void_p(0), 0]
+    assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), name
+    if tuple(t.shape) == tuple(tail):
+        return [C.c_void_p(t.data_ptr()), 0]
+    assert tuple(t.shape) == (B, *tail), (name, tuple(t.shape), (B, *tail))
+    return [C.c_void_p(t.data_ptr()), int(np.prod(tail))]
+
+
+def _dev_ins(fields, B):
+    """:func:`_dev_in` of each ``(name, tensor, tail)``, flat."""
+    return [v for name, t, tail in fields for v in _dev_in(t, tail, B, name)]
+
+
+def _dev_outs(out, shapes):
+    """Pointers of the given device outputs (null where absent), each checked against its
+    shape; info and nsat are int32, every other float64."""
+    import torch  # plumbing only
+
+    ptrs = []
+    for k, shp in shapes:
+        t = out.get(k)
+        if t is not None:
+            dt = torch.int32 if k in ("info", "nsat") else torch.float64
+            assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == tuple(shp), k
+        ptrs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
+    return ptrs
+
+
+def _first_out(out, keys, caller):
+    """The first of the outputs ``keys`` that ``out`` holds: it carries the batch size."""
+    for k in keys:
+        if out.get(k) is not None:
+            return out[k]
+    raise ValueError(f"{caller}: out holds none of " + ", ".join(keys))
+
+
+def _stream_ptr(stream):
+    import torch  # plumbing only
+
+    return C.c_void_p((torch.cuda.current_stream() if stream is None else stream).cuda_stream)
+
+
 def make_options(opts: dict | None) -> _lib.Options:
     """IPOPT option dict (CasADi ``opts['ipopt']``) -> C options struct."""
     o = _lib.default_options()
@@ -145,6 +201,47 @@ class Solver:
             return cols, n
         raise ValueError(f"{name}: expected a vector or an (n,B) matrix")
 
+    @staticmethod
+    def _batch(B, name, rows, grow=True):
+        """The batch size after an argument of ``rows`` scenarios: it must match B, which (with
+        ``grow``) may still be the 1 of shared arguments alone."""
+        if rows != B and not (grow and B == 1):
+            raise ValueError(f"{name}: batch size {rows} does not match {B}")
+        return rows
+
+    def _host_ins(self, fields, B=1, grow=True):
+        """NumPy inputs ``[(name, value, n, required)]`` as ``[(array, ld)]`` (an absent optional
+        one ``(None, 0)``), and the batch size they carry."""
+        ins = []
+        for name, v, n, required in fields:
+            if v is None:
+                if required:
+                    raise ValueError(f"{name} is required")
+                ins.append((None, 0))
+                continue
+            a, ld = self._arg(v, n, 0.0, name)
+            if ld:
+                B = self._batch(B, name, a.shape[0], grow)
+            ins.append((a, ld))
+        return ins, B
+
+    def _host_seeds(self, fields, B, what, grow=True):
+        """Seeds or right-hand sides ``[(name, value, n)]``, each (n,), (n,k) or (n,k,B) or absent,
+        as ``[(array, ld)]`` in :meth:`_rhs`' layout, their common k (None: all absent) and B."""
+        k, ins = None, []
+        for name, r, n in fields:
+            if r is None:
+                ins.append((None, 0))
+                continue
+            a, ld, kk = self._rhs(r, n, name)
+            if k not in (None, kk):
+                raise ValueError(f"{name}: {kk} {what} do not match {k}")
+            k = kk
+            if ld:
+                B = self._batch(B, name, a.shape[0], grow)
+            ins.append((a, ld))
+        return ins, k, B
+
     def __call__(self, x0=None, lbx=None, ubx=None, lbg=None, ubg=None, p=None, lam_x0=None, lam_g0=None):
         # lam_x0 / lam_g0 are accepted and, exactly as IPOPT does under its default
         # warm_start_init_point='no' (the reference sets no warm-start option,
@@ -212,32 +309,17 @@ class Solver:
         ``reserve_equality(B)`` first, otherwise every scenario reports status -102
         (Insufficient_Memory) with NaN x and f.
         """
-        import torch  # plumbing only: device memory and streams
-
-        L = _lib.lib()
         B = out["x"].shape[0]
-
-        def dv(t, n):
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous()
-            if t.dim() == 1:
-                assert t.shape[0] == n
-                return C.c_void_p(t.data_ptr()), 0
-            assert t.shape == (B, n), (tuple(t.shape), (B, n))
-            return C.c_void_p(t.data_ptr()), n
-
-        ins = []
-        for t, n in ((x0, self.nw), (lbx, self.nw), (ubx, self.nw), (lbg, self.ng), (ubg, self.ng), (p, self.np)):
-            ins += list(dv(t, n))
+        ins = _dev_ins((("x0", x0, (self.nw,)), ("lbx", lbx, (self.nw,)), ("ubx", ubx, (self.nw,)),
+                        ("lbg", lbg, (self.ng,)), ("ubg", ubg, (self.ng,)), ("p", p, (self.np,))), B)
 
         def op(k):
             t = out.get(k)
             return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
-        if stream is None:
-            stream = torch.cuda.current_stream()
-        _lib.check(L.nmpc_solve_batch_dev(self._h, B, *ins, op("x"), op("f"), op("g"), op("lam_x"),
-                                          op("lam_g"), op("lam_p"), op("X"), op("status"), op("iters"),
-                                          C.c_void_p(stream.cuda_stream)))
+        _lib.check(_lib.lib().nmpc_solve_batch_dev(self._h, B, *ins, op("x"), op("f"), op("g"), op("lam_x"),
+                                                   op("lam_g"), op("lam_p"), op("X"), op("status"), op("iters"),
+                                                   _stream_ptr(stream)))
 
     # ---- evaluation at given points (nmpc_eval_batch: CasADi's nlp_f / nlp_g / nlp_grad_f)
     def evaluate(self, x, p, lam_g=None, lam_x=None, lbx=None, ubx=None, lbg=None, ubg=None):
@@ -249,31 +331,19 @@ class Solver:
         infinite) the result also has ``kkt`` (5,B): rows stat = |grad_l|_inf, gmax =
         |grad_f|_inf, viol, compl, lmax (unnormalised; see nmpc_eval_batch_dev)."""
         want_kkt = any(v is not None for v in (lbx, ubx, lbg, ubg))
-        args, B = [], 1
-        for name, v, n, dflt in (("x", x, self.nw, None), ("p", p, self.np, None), ("lam_g", lam_g, self.ng, None),
-                                 ("lam_x", lam_x, self.nw, None), ("lbx", lbx, self.nw, -np.inf),
-                                 ("ubx", ubx, self.nw, np.inf), ("lbg", lbg, self.ng, -np.inf),
-                                 ("ubg", ubg, self.ng, np.inf)):
-            if v is None and (dflt is None or not want_kkt):
-                if name in ("x", "p"):
-                    raise ValueError(f"{name} is required")
-                args.append((None, 0))
-                continue
-            a, ld = self._arg(v, n, dflt, name)
-            if ld:
-                if B not in (1, a.shape[0]):
-                    raise ValueError(f"{name}: batch size {a.shape[0]} does not match {B}")
-                B = a.shape[0]
-            args.append((a, ld))
+        if want_kkt:  # an absent bound is infinite
+            lbx, lbg = (-np.inf if v is None else v for v in (lbx, lbg))
+            ubx, ubg = (np.inf if v is None else v for v in (ubx, ubg))
+        ins, B = self._host_ins((("x", x, self.nw, True), ("p", p, self.np, True), ("lam_g", lam_g, self.ng, False),
+                                 ("lam_x", lam_x, self.nw, False), ("lbx", lbx, self.nw, False),
+                                 ("ubx", ubx, self.nw, False), ("lbg", lbg, self.ng, False),
+                                 ("ubg", ubg, self.ng, False)))
         out = {"f": np.empty(B), "g": np.empty((B, self.ng)), "X": np.empty((B, self.nX)),
                "grad_f": np.empty((B, self.nw)), "grad_l": np.empty((B, self.nw))}
         if want_kkt:
             out["kkt"] = np.empty((B, 5))
-        ins = []
-        for a, ld in args:
-            ins += [_dptr(a) if a is not None else None, ld]
         _lib.check(_lib.lib().nmpc_eval_batch(
-            self._h, B, *ins, _dptr(out["f"]), _dptr(out["g"]), _dptr(out["X"]), _dptr(out["grad_f"]),
+            self._h, B, *_flat_ins(ins), _dptr(out["f"]), _dptr(out["g"]), _dptr(out["X"]), _dptr(out["grad_f"]),
             _dptr(out["grad_l"]), _dptr(out["kkt"]) if want_kkt else None))
         res = {k: v.T for k, v in out.items() if k != "f"}
         res["f"] = out["f"].reshape(1, B)
@@ -285,37 +355,13 @@ class Solver:
         or shared (n,).  ``out`` holds preallocated device tensors, any of f (B,), g (B,ng),
         X (B,nX), grad_f (B,nw), grad_l (B,nw), kkt (B,5) (kkt needs all four bounds).
         Enqueued on ``stream`` (default = current); never synchronises the host."""
-        import torch  # plumbing only: device memory and streams
-
         keys = ("f", "g", "X", "grad_f", "grad_l", "kkt")
-        given = [out[k] for k in keys if out.get(k) is not None]
-        if not given:
-            raise ValueError("evaluate_device: out holds none of " + ", ".join(keys))
-        B = given[0].shape[0]
-
-        def dv(t, n):
-            if t is None:
-                return C.c_void_p(0), 0
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous()
-            if t.dim() == 1:
-                assert t.shape[0] == n
-                return C.c_void_p(t.data_ptr()), 0
-            assert t.shape == (B, n), (tuple(t.shape), (B, n))
-            return C.c_void_p(t.data_ptr()), n
-
-        ins = []
-        for t, n in ((x, self.nw), (p, self.np), (lam_g, self.ng), (lam_x, self.nw), (lbx, self.nw), (ubx, self.nw),
-                     (lbg, self.ng), (ubg, self.ng)):
-            ins += list(dv(t, n))
-        outs = []
-        for k, shp in zip(keys, ((B,), (B, self.ng), (B, self.nX), (B, self.nw), (B, self.nw), (B, 5))):
-            t = out.get(k)
-            if t is not None:
-                assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp, k
-            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
-        if stream is None:
-            stream = torch.cuda.current_stream()
-        _lib.check(_lib.lib().nmpc_eval_batch_dev(self._h, B, *ins, *outs, C.c_void_p(stream.cuda_stream)))
+        B = _first_out(out, keys, "evaluate_device").shape[0]
+        ins = _dev_ins((("x", x, (self.nw,)), ("p", p, (self.np,)), ("lam_g", lam_g, (self.ng,)),
+                        ("lam_x", lam_x, (self.nw,)), ("lbx", lbx, (self.nw,)), ("ubx", ubx, (self.nw,)),
+                        ("lbg", lbg, (self.ng,)), ("ubg", ubg, (self.ng,))), B)
+        outs = _dev_outs(out, zip(keys, ((B,), (B, self.ng), (B, self.nX), (B, self.nw), (B, self.nw), (B, 5))))
+        _lib.check(_lib.lib().nmpc_eval_batch_dev(self._h, B, *ins, *outs, _stream_ptr(stream)))
 
     def certify(self, sol: dict, lbx, ubx, lbg, ubg, p):
         """First-order certificate of a result of ``__call__`` that does not come from the
@@ -336,32 +382,21 @@ class Solver:
                 "kkt": ev["kkt"]}
 
     # ---- products at given points (nmpc_products_batch: CasADi's nlp_jac_g / nlp_hess_l on vectors)
-    def _products(self, x, p, v, ld_v, nv, lam_g, obj_factor, want=("jv", "hv", "dX")):
-        """v: (1 or B, nv, nw) C-contiguous, ld_v 0 or nw * nv.  Returns (B, nv, n) arrays."""
-        args, B = [], 1
-        for name, a, n in (("x", x, self.nw), ("p", p, self.np), ("lam_g", lam_g, self.ng)):
-            if a is None:
-                if name != "lam_g":
-                    raise ValueError(f"{name} is required")
-                args.append((None, 0))
-                continue
-            a, ld = self._arg(a, n, 0.0, name)
-            if ld:
-                if B not in (1, a.shape[0]):
-                    raise ValueError(f"{name}: batch size {a.shape[0]} does not match {B}")
-                B = a.shape[0]
-            args.append((a, ld))
-        if ld_v:
-            if B not in (1, v.shape[0]):
-                raise ValueError(f"v: batch size {v.shape[0]} does not match {B}")
-            B = v.shape[0]
+    def _xpl(self, x, p, lam_g):
+        """The inputs every entry point at given points starts with: :meth:`_host_ins`' fields."""
+        return ("x", x, self.nw, True), ("p", p, self.np, True), ("lam_g", lam_g, self.ng, False)
+
+    def _xpl_device(self, x, p, lam_g, B):
+        return _dev_ins((("x", x, (self.nw,)), ("p", p, (self.np,)), ("lam_g", lam_g, (self.ng,))), B)
+
+    def _products(self, x, p, d, lam_g, obj_factor, want=("jv", "hv", "dX")):
+        """d: the directions as :meth:`_dp_dirs` returns them.  Returns (B, nv, n) arrays."""
+        ins, B = self._host_ins(self._xpl(x, p, lam_g))
+        v, B = self._dp_arg(d, B, "v", grow=True)
         sizes = {"jv": self.ng, "hv": self.nw, "dX": self.nX}
-        out = {k: np.empty((B, nv, sizes[k])) for k in want}
-        ins = []
-        for a, ld in args:
-            ins += [_dptr(a) if a is not None else None, ld]
+        out = {k: np.empty((B, d.shape[1], sizes[k])) for k in want}
         _lib.check(_lib.lib().nmpc_products_batch(
-            self._h, B, nv, *ins, float(obj_factor), _dptr(v), ld_v,
+            self._h, B, d.shape[1], *_flat_ins(ins), float(obj_factor), *_flat_ins([v]),
             *[_dptr(out[k]) if k in out else None for k in ("jv", "hv", "dX")]))
         return out
 
@@ -371,17 +406,7 @@ class Solver:
         (CasADi's ``hess_l`` convention, lam_g absent = zeros) and ``dX`` (nX,nv,B) = (dX/dw) v,
         the tangent of the rollout.  x, p, lam_g as :meth:`evaluate`'s; ``v`` is one direction
         (nw,), directions (nw,nv) shared by the batch, or (nw,nv,B)."""
-        a = np.asarray(v, dtype=np.float64)
-        if a.ndim == 1:
-            a = a.reshape(-1, 1)
-        if a.ndim not in (2, 3) or a.shape[0] != self.nw or a.shape[1] < 1:
-            raise ValueError(f"v: expected ({self.nw},), ({self.nw},nv) or ({self.nw},nv,B), got shape {a.shape}")
-        nv = a.shape[1]
-        if a.ndim == 2:
-            vv, ld_v = np.ascontiguousarray(a.T).reshape(1, nv, self.nw), 0
-        else:
-            vv, ld_v = np.ascontiguousarray(a.transpose(2, 1, 0)), self.nw * nv
-        out = self._products(x, p, vv, ld_v, nv, lam_g, obj_factor)
+        out = self._products(x, p, self._dp_dirs(v, 1, self.nw, "v")[0], lam_g, obj_factor)
         return {k: np.ascontiguousarray(t.transpose(2, 1, 0)) for k, t in out.items()}
 
     def products_device(self, x, p, v, out: dict, lam_g=None, obj_factor=1.0, stream=None):
@@ -389,86 +414,38 @@ class Solver:
         scenario-major (B, n) or shared (n,); ``v`` is (B, nv, nw) or shared (nv, nw); ``out``
         holds preallocated device tensors, any of jv (B,nv,ng), hv (B,nv,nw), dX (B,nv,nX).
         Enqueued on ``stream`` (default = current); never synchronises the host."""
-        import torch  # plumbing only: device memory and streams
-
         keys = ("jv", "hv", "dX")
-        given = [out[k] for k in keys if out.get(k) is not None]
-        if not given:
-            raise ValueError("products_device: out holds none of " + ", ".join(keys))
-        B, nv = given[0].shape[0], given[0].shape[1]
-
-        def dv(t, n):
-            if t is None:
-                return C.c_void_p(0), 0
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous()
-            if t.dim() == 1:
-                assert t.shape[0] == n
-                return C.c_void_p(t.data_ptr()), 0
-            assert t.shape == (B, n), (tuple(t.shape), (B, n))
-            return C.c_void_p(t.data_ptr()), n
-
-        ins = []
-        for t, n in ((x, self.nw), (p, self.np), (lam_g, self.ng)):
-            ins += list(dv(t, n))
-        assert v.dtype == torch.float64 and v.is_cuda and v.is_contiguous()
-        assert tuple(v.shape) in ((nv, self.nw), (B, nv, self.nw)), tuple(v.shape)
-        ld_v = 0 if v.dim() == 2 else nv * self.nw
-        outs = []
-        for k, n in zip(keys, (self.ng, self.nw, self.nX)):
-            t = out.get(k)
-            if t is not None:
-                assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B, nv, n), k
-            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
-        if stream is None:
-            stream = torch.cuda.current_stream()
-        _lib.check(_lib.lib().nmpc_products_batch_dev(self._h, B, nv, *ins, float(obj_factor),
-                                                      C.c_void_p(v.data_ptr()), ld_v, *outs,
-                                                      C.c_void_p(stream.cuda_stream)))
+        B, nv = _first_out(out, keys, "products_device").shape[:2]
+        outs = _dev_outs(out, zip(keys, ((B, nv, self.ng), (B, nv, self.nw), (B, nv, self.nX))))
+        _lib.check(_lib.lib().nmpc_products_batch_dev(
+            self._h, B, nv, *self._xpl_device(x, p, lam_g, B), float(obj_factor),
+            *_dev_in(v, (nv, self.nw), B, "v"), *outs, _stream_ptr(stream)))
 
     def jacobian(self, x, p):
         """Dense J_g (ng,nw,B) at the given decision vectors (CasADi's ``nlp_jac_g``): the
         identity directions, shared by the batch, through :meth:`products`' kernel."""
-        eye = np.eye(self.nw).reshape(1, self.nw, self.nw)
-        out = self._products(x, p, eye, 0, self.nw, None, 1.0, want=("jv",))
+        out = self._products(x, p, np.eye(self.nw), None, 1.0, want=("jv",))
         return np.ascontiguousarray(out["jv"].transpose(2, 1, 0))
 
     def hessian(self, x, p, lam_g=None, obj_factor=1.0):
         """Dense Hessian of the Lagrangian (nw,nw,B), obj_factor grad^2 f + sum lam_g_i grad^2 g_i
         (CasADi's ``nlp_hess_l``, the full symmetric matrix), column d being W e_d."""
-        eye = np.eye(self.nw).reshape(1, self.nw, self.nw)
-        out = self._products(x, p, eye, 0, self.nw, lam_g, obj_factor, want=("hv",))
+        out = self._products(x, p, np.eye(self.nw), lam_g, obj_factor, want=("hv",))
         return np.ascontiguousarray(out["hv"].transpose(2, 1, 0))
 
     # ---- parameter-direction products at given points (nmpc_param_products_batch)
-    def _param_products(self, x, p, dp, ld_dp, nd, lam_g, obj_factor, want=("jp", "hp", "dXp", "gp")):
-        """dp: (1 or B, nd, np) C-contiguous, ld_dp 0 or np * nd (None with nd = 0).  Returns
-        (B, nd, n) arrays, and gp as (B, np)."""
-        args, B = [], 1
-        for name, a, n in (("x", x, self.nw), ("p", p, self.np), ("lam_g", lam_g, self.ng)):
-            if a is None:
-                if name != "lam_g":
-                    raise ValueError(f"{name} is required")
-                args.append((None, 0))
-                continue
-            a, ld = self._arg(a, n, 0.0, name)
-            if ld:
-                if B not in (1, a.shape[0]):
-                    raise ValueError(f"{name}: batch size {a.shape[0]} does not match {B}")
-                B = a.shape[0]
-            args.append((a, ld))
-        if ld_dp:
-            if B not in (1, dp.shape[0]):
-                raise ValueError(f"dp: batch size {dp.shape[0]} does not match {B}")
-            B = dp.shape[0]
+    def _param_products(self, x, p, d, lam_g, obj_factor, want=("jp", "hp", "dXp", "gp")):
+        """d: the directions as :meth:`_dp_dirs` returns them, or None for none (nd = 0).
+        Returns (B, nd, n) arrays, and gp as (B, np)."""
+        ins, B = self._host_ins(self._xpl(x, p, lam_g))
+        dp, B = ((None, 0), B) if d is None else self._dp_arg(d, B, grow=True)
+        nd = 0 if d is None else d.shape[1]
         sizes = {"jp": self.ng, "hp": self.nw, "dXp": self.nX}
         out = {k: np.empty((B, nd, sizes[k])) for k in want if k != "gp"}
         if "gp" in want:
             out["gp"] = np.empty((B, self.np))
-        ins = []
-        for a, ld in args:
-            ins += [_dptr(a) if a is not None else None, ld]
         _lib.check(_lib.lib().nmpc_param_products_batch(
-            self._h, B, nd, *ins, float(obj_factor), _dptr(dp) if dp is not None else None, ld_dp,
+            self._h, B, nd, *_flat_ins(ins), float(obj_factor), *_flat_ins([dp]),
             *[_dptr(out[k]) if k in out else None for k in ("jp", "hp", "dXp", "gp")]))
         return out
 
@@ -482,19 +459,9 @@ class Solver:
         reads give exactly 0 in gp, and their entries of dp are never read.  ``dp=None`` asks
         for ``gp`` alone (no directions)."""
         if dp is None:
-            out = self._param_products(x, p, None, 0, 0, lam_g, obj_factor, want=("gp",))
+            out = self._param_products(x, p, None, lam_g, obj_factor, want=("gp",))
             return {"gp": np.ascontiguousarray(out["gp"].T)}
-        a = np.asarray(dp, dtype=np.float64)
-        if a.ndim == 1:
-            a = a.reshape(-1, 1)
-        if a.ndim not in (2, 3) or a.shape[0] != self.np or a.shape[1] < 1:
-            raise ValueError(f"dp: expected ({self.np},), ({self.np},nd) or ({self.np},nd,B), got shape {a.shape}")
-        nd = a.shape[1]
-        if a.ndim == 2:
-            dd, ld_dp = np.ascontiguousarray(a.T).reshape(1, nd, self.np), 0
-        else:
-            dd, ld_dp = np.ascontiguousarray(a.transpose(2, 1, 0)), self.np * nd
-        out = self._param_products(x, p, dd, ld_dp, nd, lam_g, obj_factor)
+        out = self._param_products(x, p, self._dp_dirs(dp, 1)[0], lam_g, obj_factor)
         return {k: np.ascontiguousarray(t.transpose(2, 1, 0) if t.ndim == 3 else t.T) for k, t in out.items()}
 
     def param_products_device(self, x, p, dp, out: dict, lam_g=None, obj_factor=1.0, stream=None):
@@ -503,63 +470,26 @@ class Solver:
         when only gp is asked for; ``out`` holds preallocated device tensors, any of jp (B,nd,ng),
         hp (B,nd,nw), dXp (B,nd,nX), gp (B,np).  Enqueued on ``stream`` (default = current);
         never synchronises the host."""
-        import torch  # plumbing only: device memory and streams
-
-        keys = ("jp", "hp", "dXp")
-        given = [out[k] for k in keys if out.get(k) is not None]
-        gp = out.get("gp")
-        if not given and gp is None:
-            raise ValueError("param_products_device: out holds none of " + ", ".join(keys + ("gp",)))
-        if given and dp is None:
+        keys = ("jp", "hp", "dXp", "gp")
+        first = _first_out(out, keys, "param_products_device")
+        if first is not out.get("gp") and dp is None:
             raise ValueError("param_products_device: dp is required for a directional output")
-        B = given[0].shape[0] if given else gp.shape[0]
-        nd = 0 if dp is None else dp.shape[-2]
-
-        def dv(t, n):
-            if t is None:
-                return C.c_void_p(0), 0
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous()
-            if t.dim() == 1:
-                assert t.shape[0] == n
-                return C.c_void_p(t.data_ptr()), 0
-            assert t.shape == (B, n), (tuple(t.shape), (B, n))
-            return C.c_void_p(t.data_ptr()), n
-
-        ins = []
-        for t, n in ((x, self.nw), (p, self.np), (lam_g, self.ng)):
-            ins += list(dv(t, n))
-        if dp is None:
-            dpp, ld_dp = C.c_void_p(0), 0
-        else:
-            assert dp.dtype == torch.float64 and dp.is_cuda and dp.is_contiguous()
-            assert tuple(dp.shape) in ((nd, self.np), (B, nd, self.np)), tuple(dp.shape)
-            dpp, ld_dp = C.c_void_p(dp.data_ptr()), (0 if dp.dim() == 2 else nd * self.np)
-        outs = []
-        for k, n in zip(keys, (self.ng, self.nw, self.nX)):
-            t = out.get(k)
-            if t is not None:
-                assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B, nd, n), k
-            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
-        if gp is not None:
-            assert gp.dtype == torch.float64 and gp.is_cuda and gp.is_contiguous() and tuple(gp.shape) == (B, self.np)
-        outs.append(C.c_void_p(gp.data_ptr()) if gp is not None else C.c_void_p(0))
-        if stream is None:
-            stream = torch.cuda.current_stream()
-        _lib.check(_lib.lib().nmpc_param_products_batch_dev(self._h, B, nd, *ins, float(obj_factor), dpp, ld_dp,
-                                                            *outs, C.c_void_p(stream.cuda_stream)))
+        B, nd = first.shape[0], (0 if dp is None else dp.shape[-2])
+        outs = _dev_outs(out, zip(keys, ((B, nd, self.ng), (B, nd, self.nw), (B, nd, self.nX), (B, self.np))))
+        _lib.check(_lib.lib().nmpc_param_products_batch_dev(
+            self._h, B, nd, *self._xpl_device(x, p, lam_g, B), float(obj_factor),
+            *_dev_in(dp, (nd, self.np), B, "dp"), *outs, _stream_ptr(stream)))
 
     def param_jacobian(self, x, p):
         """Dense dg/dp (ng,np,B) at the given points: the identity directions, shared by the
         batch, through :meth:`param_products`' kernel."""
-        eye = np.eye(self.np).reshape(1, self.np, self.np)
-        out = self._param_products(x, p, eye, 0, self.np, None, 1.0, want=("jp",))
+        out = self._param_products(x, p, np.eye(self.np), None, 1.0, want=("jp",))
         return np.ascontiguousarray(out["jp"].transpose(2, 1, 0))
 
     def param_cross(self, x, p, lam_g=None, obj_factor=1.0):
         """Dense d_p grad_w L (nw,np,B), L = obj_factor f + lam_g' g, column d being the
         derivative with respect to p_d (its transpose applied to y serves reverse mode)."""
-        eye = np.eye(self.np).reshape(1, self.np, self.np)
-        out = self._param_products(x, p, eye, 0, self.np, lam_g, obj_factor, want=("hp",))
+        out = self._param_products(x, p, np.eye(self.np), lam_g, obj_factor, want=("hp",))
         return np.ascontiguousarray(out["hp"].transpose(2, 1, 0))
 
     # ---- adjoint (transposed) products at given points (nmpc_adjoint_products_batch)
@@ -574,36 +504,8 @@ class Solver:
         (n,), seeds (n,na) shared by the batch, or (n,na,B); an absent seed contributes nothing,
         at least one is required and all given ones carry the same na.  Entries of p that
         nothing reads give exactly 0 in pbar.  ``want`` names the outputs to form."""
-        args, B = [], 1
-
-        def batch(name, rows):
-            nonlocal B
-            if B not in (1, rows):
-                raise ValueError(f"{name}: batch size {rows} does not match {B}")
-            B = rows
-
-        for name, a, n in (("x", x, self.nw), ("p", p, self.np), ("lam_g", lam_g, self.ng)):
-            if a is None:
-                if name != "lam_g":
-                    raise ValueError(f"{name} is required")
-                args.append((None, 0))
-                continue
-            a, ld = self._arg(a, n, 0.0, name)
-            if ld:
-                batch(name, a.shape[0])
-            args.append((a, ld))
-        na, seeds = None, []
-        for name, r, n in (("y", y, self.ng), ("z", z, self.nw), ("Xbar", Xbar, self.nX)):
-            if r is None:
-                seeds.append((None, 0))
-                continue
-            a, ld, k = self._rhs(r, n, name)
-            if na not in (None, k):
-                raise ValueError(f"{name}: {k} seeds do not match {na}")
-            na = k
-            if ld:
-                batch(name, a.shape[0])
-            seeds.append((a, ld))
+        ins, B = self._host_ins(self._xpl(x, p, lam_g))
+        seeds, na, B = self._host_seeds((("y", y, self.ng), ("z", z, self.nw), ("Xbar", Xbar, self.nX)), B, "seeds")
         if na is None:
             raise ValueError("y, z or Xbar is required")
         want = tuple(want)
@@ -611,14 +513,9 @@ class Solver:
             raise ValueError(f"want: expected 'wbar' and / or 'pbar', got {want!r}")
         sizes = {"wbar": self.nw, "pbar": self.np}
         out = {k: np.empty((B, na, sizes[k])) for k in ("wbar", "pbar") if k in want}
-        ins = []
-        for a, ld in args:
-            ins += [_dptr(a) if a is not None else None, ld]
-        ins.append(float(obj_factor))
-        for a, ld in seeds:
-            ins += [_dptr(a) if a is not None else None, ld]
         _lib.check(_lib.lib().nmpc_adjoint_products_batch(
-            self._h, B, na, *ins, *[_dptr(out[k]) if k in out else None for k in ("wbar", "pbar")]))
+            self._h, B, na, *_flat_ins(ins), float(obj_factor), *_flat_ins(seeds),
+            *[_dptr(out[k]) if k in out else None for k in ("wbar", "pbar")]))
         return {k: np.ascontiguousarray(t.transpose(2, 1, 0)) for k, t in out.items()}
 
     def adjoint_products_device(self, x, p, out: dict, y=None, z=None, Xbar=None, lam_g=None, obj_factor=1.0,
@@ -627,48 +524,15 @@ class Solver:
         scenario-major (B, n) or shared (n,); each seed is (B, na, n) or shared (na, n), or None;
         ``out`` holds preallocated device tensors, wbar (B,na,nw) and / or pbar (B,na,np).
         Enqueued on ``stream`` (default = current); never synchronises the host."""
-        import torch  # plumbing only: device memory and streams
-
         keys = ("wbar", "pbar")
-        given = [out[k] for k in keys if out.get(k) is not None]
-        if not given:
-            raise ValueError("adjoint_products_device: out holds none of " + ", ".join(keys))
+        first = _first_out(out, keys, "adjoint_products_device")
         if y is None and z is None and Xbar is None:
             raise ValueError("y, z or Xbar is required")
-        B, na = given[0].shape[0], given[0].shape[1]
-
-        def dv(t, n):
-            if t is None:
-                return C.c_void_p(0), 0
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous()
-            if t.dim() == 1:
-                assert t.shape[0] == n
-                return C.c_void_p(t.data_ptr()), 0
-            assert t.shape == (B, n), (tuple(t.shape), (B, n))
-            return C.c_void_p(t.data_ptr()), n
-
-        def sv(t, n, name):
-            if t is None:
-                return C.c_void_p(0), 0
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), name
-            assert tuple(t.shape) in ((na, n), (B, na, n)), (name, tuple(t.shape))
-            return C.c_void_p(t.data_ptr()), (0 if t.dim() == 2 else na * n)
-
-        ins = []
-        for t, n in ((x, self.nw), (p, self.np), (lam_g, self.ng)):
-            ins += list(dv(t, n))
-        ins.append(float(obj_factor))
-        ins += list(sv(y, self.ng, "y")) + list(sv(z, self.nw, "z")) + list(sv(Xbar, self.nX, "Xbar"))
-        outs = []
-        for k, n in zip(keys, (self.nw, self.np)):
-            t = out.get(k)
-            if t is not None:
-                assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B, na, n), k
-            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
-        if stream is None:
-            stream = torch.cuda.current_stream()
-        _lib.check(_lib.lib().nmpc_adjoint_products_batch_dev(self._h, B, na, *ins, *outs,
-                                                              C.c_void_p(stream.cuda_stream)))
+        B, na = first.shape[:2]
+        seeds = _dev_ins((("y", y, (na, self.ng)), ("z", z, (na, self.nw)), ("Xbar", Xbar, (na, self.nX))), B)
+        outs = _dev_outs(out, zip(keys, ((B, na, self.nw), (B, na, self.np))))
+        _lib.check(_lib.lib().nmpc_adjoint_products_batch_dev(
+            self._h, B, na, *self._xpl_device(x, p, lam_g, B), float(obj_factor), *seeds, *outs, _stream_ptr(stream)))
 
     # ---- condensed KKT solves at given points (nmpc_kkt_solve_batch: the Newton-step operator)
     def _rhs(self, r, n: int, name: str):
@@ -698,54 +562,20 @@ class Solver:
         -11 the scenario's other outputs are NaN."""
         if r_w is None and r_g is None:
             raise ValueError("r_w or r_g is required")
-        args, B = [], 1
-
-        def batch(name, rows):
-            nonlocal B
-            if B not in (1, rows):
-                raise ValueError(f"{name}: batch size {rows} does not match {B}")
-            B = rows
-
-        for name, a, n in (("x", x, self.nw), ("p", p, self.np), ("lam_g", lam_g, self.ng),
-                           ("sigma_x", sigma_x, self.nw), ("sigma_s", sigma_s, self.ng)):
-            if a is None:
-                if name in ("x", "p"):
-                    raise ValueError(f"{name} is required")
-                args.append((None, 0))
-                continue
-            a, ld = self._arg(a, n, 0.0, name)
-            if ld:
-                batch(name, a.shape[0])
-            args.append((a, ld))
-        if delta is None:
-            dl, ld_dl = None, 0
-        else:
-            dl = np.ascontiguousarray(np.asarray(delta, dtype=np.float64).reshape(-1))
-            ld_dl = 0 if dl.shape[0] == 1 else 1
-            if ld_dl:
-                batch("delta", dl.shape[0])
-        nr, rhs = None, []
-        for name, r, n in (("r_w", r_w, self.nw), ("r_g", r_g, self.ng)):
-            if r is None:
-                rhs.append((None, 0))
-                continue
-            a, ld, k = self._rhs(r, n, name)
-            if nr not in (None, k):
-                raise ValueError(f"{name}: {k} right-hand sides do not match {nr}")
-            nr = k
-            if ld:
-                batch(name, a.shape[0])
-            rhs.append((a, ld))
+        ins, B = self._host_ins(self._xpl(x, p, lam_g) + (("sigma_x", sigma_x, self.nw, False),
+                                                          ("sigma_s", sigma_s, self.ng, False)))
+        dl = (None, 0)
+        if delta is not None:
+            d = np.ascontiguousarray(np.asarray(delta, dtype=np.float64).reshape(-1))
+            dl = (d, 0 if d.shape[0] == 1 else 1)
+            if dl[1]:
+                B = self._batch(B, "delta", d.shape[0])
+        rhs, nr, B = self._host_seeds((("r_w", r_w, self.nw), ("r_g", r_g, self.ng)), B, "right-hand sides")
         out = {"dw": np.empty((B, nr, self.nw)), "dX": np.empty((B, nr, self.nX)), "jdw": np.empty((B, nr, self.ng))}
         info = np.empty(B, dtype=np.int32)
-        ins = []
-        for a, ld in args[:3]:
-            ins += [_dptr(a) if a is not None else None, ld]
-        ins.append(float(obj_factor))
-        for a, ld in args[3:] + [(dl, ld_dl)] + rhs:
-            ins += [_dptr(a) if a is not None else None, ld]
         _lib.check(_lib.lib().nmpc_kkt_solve_batch(
-            self._h, B, nr, *ins, _dptr(out["dw"]), _dptr(out["dX"]), _dptr(out["jdw"]), info.ctypes.data_as(_IP)))
+            self._h, B, nr, *_flat_ins(ins[:3]), float(obj_factor), *_flat_ins(ins[3:] + [dl] + rhs),
+            _dptr(out["dw"]), _dptr(out["dX"]), _dptr(out["jdw"]), info.ctypes.data_as(_IP)))
         res = {k: np.ascontiguousarray(t.transpose(2, 1, 0)) for k, t in out.items()}
         res["info"] = info
         return res
@@ -758,59 +588,19 @@ class Solver:
         preallocated device tensors, any of dw (B,nr,nw), dX (B,nr,nX), jdw (B,nr,ng) and
         info (B,) int32 (at least one of the first three).  Enqueued on ``stream`` (default =
         current); never synchronises the host."""
-        import torch  # plumbing only: device memory and streams
-
         keys = ("dw", "dX", "jdw")
-        given = [out[k] for k in keys if out.get(k) is not None]
-        if not given:
-            raise ValueError("kkt_solve_device: out holds none of " + ", ".join(keys))
+        first = _first_out(out, keys, "kkt_solve_device")
         if r_w is None and r_g is None:
             raise ValueError("r_w or r_g is required")
-        B, nr = given[0].shape[0], given[0].shape[1]
-
-        def dv(t, n):
-            if t is None:
-                return C.c_void_p(0), 0
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous()
-            if t.dim() == 1:
-                assert t.shape[0] == n
-                return C.c_void_p(t.data_ptr()), 0
-            assert t.shape == (B, n), (tuple(t.shape), (B, n))
-            return C.c_void_p(t.data_ptr()), n
-
-        def rv(t, n, name):
-            if t is None:
-                return C.c_void_p(0), 0
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), name
-            assert tuple(t.shape) in ((nr, n), (B, nr, n)), (name, tuple(t.shape))
-            return C.c_void_p(t.data_ptr()), (0 if t.dim() == 2 else nr * n)
-
-        ins = []
-        for t, n in ((x, self.nw), (p, self.np), (lam_g, self.ng)):
-            ins += list(dv(t, n))
-        ins.append(float(obj_factor))
-        for t, n in ((sigma_x, self.nw), (sigma_s, self.ng)):
-            ins += list(dv(t, n))
-        if delta is None:
-            ins += [C.c_void_p(0), 0]
-        else:
-            assert delta.dtype == torch.float64 and delta.is_cuda and delta.is_contiguous()
-            assert tuple(delta.shape) in ((1,), (B,)), tuple(delta.shape)
-            ins += [C.c_void_p(delta.data_ptr()), 0 if delta.shape[0] == 1 else 1]
-        ins += list(rv(r_w, self.nw, "r_w")) + list(rv(r_g, self.ng, "r_g"))
-        outs = []
-        for k, n in zip(keys, (self.nw, self.nX, self.ng)):
-            t = out.get(k)
-            if t is not None:
-                assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B, nr, n), k
-            outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
-        t = out.get("info")
-        if t is not None:
-            assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B,), "info"
-        outs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
-        if stream is None:
-            stream = torch.cuda.current_stream()
-        _lib.check(_lib.lib().nmpc_kkt_solve_batch_dev(self._h, B, nr, *ins, *outs, C.c_void_p(stream.cuda_stream)))
+        B, nr = first.shape[:2]
+        if delta is not None and tuple(delta.shape) == (1,):
+            delta = delta.reshape(())  # shared
+        rest = _dev_ins((("sigma_x", sigma_x, (self.nw,)), ("sigma_s", sigma_s, (self.ng,)), ("delta", delta, ()),
+                         ("r_w", r_w, (nr, self.nw)), ("r_g", r_g, (nr, self.ng))), B)
+        outs = _dev_outs(out, (("dw", (B, nr, self.nw)), ("dX", (B, nr, self.nX)), ("jdw", (B, nr, self.ng)),
+                               ("info", (B,))))
+        _lib.check(_lib.lib().nmpc_kkt_solve_batch_dev(
+            self._h, B, nr, *self._xpl_device(x, p, lam_g, B), float(obj_factor), *rest, *outs, _stream_ptr(stream)))
 
     def barrier_weights(self, sol: dict, lbx, ubx, lbg, ubg):
         """The barrier weights Sigma_x (nw,B) and Sigma_s (ng,B) at a result of ``__call__``,
@@ -881,8 +671,7 @@ class Solver:
             d = np.repeat(d[:, :, None], B, axis=2)
         sx, ss = self.barrier_weights(sol, lbx, ubx, lbg, ubg)
         if tangent == "exact":
-            dd = np.ascontiguousarray(d.transpose(2, 1, 0))  # (B, nd, np)
-            pp = self._param_products(x, P, dd, self.np * nd, nd, lam, 1.0, want=("jp", "hp"))
+            pp = self._param_products(x, P, d, lam, 1.0, want=("jp", "hp"))
             dgl, dg = (np.ascontiguousarray(pp[k].transpose(2, 1, 0)) for k in ("hp", "jp"))
         else:
             dgl, dg = np.empty((self.nw, nd, B)), np.empty((self.ng, nd, B))
@@ -966,93 +755,44 @@ class Solver:
                 ("ubx", ubx, self.nw), ("lbg", lbg, self.ng), ("ubg", ubg, self.ng))
 
     def _point_ins_host(self, sol, lbx, ubx, lbg, ubg, p):
-        """NumPy: the nine point inputs as ``[(array, ld)]`` (an absent one ``(None, 0)``), and B."""
-        x, ld_x = self._arg(sol["x"], self.nw, 0.0, "x")
-        B = x.shape[0]
-        ins = [(x, ld_x)]
-        for name, a, n in self._point_fields(sol, lbx, ubx, lbg, ubg, p)[1:]:
-            if a is None:
-                ins.append((None, 0))
-                continue
-            a, ld = self._arg(a, n, 0.0, name)
-            if ld and a.shape[0] != B:
-                raise ValueError(f"{name}: batch size {a.shape[0]} does not match {B}")
-            ins.append((a, ld))
-        return ins, B
-
-    @staticmethod
-    def _flat_ins(ins):
-        flat = []
-        for a, ld in ins:
-            flat += [_dptr(a) if a is not None else None, ld]
-        return flat
+        """NumPy: the nine point inputs as ``[(array, ld)]`` (an absent one ``(None, 0)``), and B
+        (x's: every other argument matches it or is shared)."""
+        fields = self._point_fields(sol, lbx, ubx, lbg, ubg, p)
+        x = self._arg(sol["x"], self.nw, 0.0, "x")
+        ins, B = self._host_ins([(*f, False) for f in fields[1:]], x[0].shape[0], grow=False)
+        return [x] + ins, B
 
     def _point_ins_device(self, sol, lbx, ubx, lbg, ubg, p, B=None):
         """torch: the nine point inputs as a flat ``[pointer, ld, ...]``, and B (the outputs'
         when given, else x's)."""
-        import torch  # plumbing only: device memory and streams
-
         for k in ("x", "lam_g", "lam_x"):
             if sol.get(k) is None:
                 raise ValueError(f"sol: {k} is required")
         if B is None:
             B = sol["x"].shape[0]
-
-        def dv(t, n, name):
-            if t is None:
-                return C.c_void_p(0), 0
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), name
-            if t.dim() == 1:
-                assert t.shape[0] == n, name
-                return C.c_void_p(t.data_ptr()), 0
-            assert t.shape == (B, n), (name, tuple(t.shape), (B, n))
-            return C.c_void_p(t.data_ptr()), n
-
-        ins = []
-        for name, t, n in self._point_fields(sol, lbx, ubx, lbg, ubg, p):
+        fields = self._point_fields(sol, lbx, ubx, lbg, ubg, p)
+        for name, t, n in fields:
             if t is None and name != "g":
                 raise ValueError(f"{name} is required")
-            ins += list(dv(t, n, name))
-        return ins, B
+        return _dev_ins([(name, t, (n,)) for name, t, n in fields], B), B
 
-    def _dp_dirs(self, dp, nd_min):
-        """``dp`` (np,), (np,nd) or (np,nd,B) as a float64 array of 2 or 3 dimensions, and nd."""
+    def _dp_dirs(self, dp, nd_min, n=None, name="dp"):
+        """Directions ``dp`` (np,), (np,nd) or (np,nd,B) -- or ``v``, of length n -- as a float64
+        array of 2 or 3 dimensions, and nd."""
+        n, cnt = self.np if n is None else n, "n" + name[0]
         d = np.asarray(dp, dtype=np.float64)
         if d.ndim == 1:
             d = d.reshape(-1, 1)
-        if d.ndim not in (2, 3) or d.shape[0] != self.np or d.shape[1] < nd_min:
-            raise ValueError(f"dp: expected ({self.np},), ({self.np},nd) or ({self.np},nd,B), got shape {d.shape}")
+        if d.ndim not in (2, 3) or d.shape[0] != n or d.shape[1] < nd_min:
+            raise ValueError(f"{name}: expected ({n},), ({n},{cnt}) or ({n},{cnt},B), got shape {d.shape}")
         return d, d.shape[1]
 
-    def _dp_arg(self, d, B):
-        """:meth:`_dp_dirs`' array in the C layout with its leading dimension."""
+    def _dp_arg(self, d, B, name="dp", grow=False):
+        """:meth:`_dp_dirs`' array in the C layout with its leading dimension, and the batch size."""
         if d.ndim == 3:
-            if d.shape[2] != B:
-                raise ValueError(f"dp: batch size {d.shape[2]} does not match {B}")
-            return np.ascontiguousarray(d.transpose(2, 1, 0)), self.np * d.shape[1]  # (B, nd, np)
-        return np.ascontiguousarray(d.T), 0  # (nd, np), shared
-
-    def _dp_device(self, dp, nd, B):
-        import torch  # plumbing only
-
-        assert dp.dtype == torch.float64 and dp.is_cuda and dp.is_contiguous(), "dp"
-        assert tuple(dp.shape) in ((nd, self.np), (B, nd, self.np)), ("dp", tuple(dp.shape))
-        return [C.c_void_p(dp.data_ptr()), 0 if dp.dim() == 2 else nd * self.np]
-
-    @staticmethod
-    def _out_ptrs_device(out, shapes):
-        """Pointers of the given device outputs (null where absent), each checked against its
-        shape; info is int32, every other float64."""
-        import torch  # plumbing only
-
-        ptrs = []
-        for k, shp in shapes:
-            t = out.get(k)
-            if t is not None:
-                dt = torch.int32 if k == "info" else torch.float64
-                assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp, k
-            ptrs.append(C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0))
-        return ptrs
+            B = self._batch(B, name, d.shape[2], grow)
+            return (np.ascontiguousarray(d.transpose(2, 1, 0)), d.shape[0] * d.shape[1]), B  # (B, nd, n)
+        return (np.ascontiguousarray(d.T), 0), B  # (nd, n), shared
 
     def _raise_equality_rows(self, info, lbg, ubg, caller):
         """info = -11 with an equality row: the ``ValueError`` of :meth:`barrier_weights`."""
@@ -1070,24 +810,15 @@ class Solver:
         host only stages the arrays.  Equality rows raise ``ValueError``, as
         :meth:`barrier_weights` does."""
         ins, B = self._point_ins_host(sol, lbx, ubx, lbg, ubg, p)
-        na = None
-        for name, r, n in (("x_bar", x_bar, self.nw), ("lam_g_bar", lam_g_bar, self.ng), ("X_bar", X_bar, self.nX)):
-            if r is None:
-                ins.append((None, 0))
-                continue
-            a, ld, k = self._rhs(r, n, name)
-            if na not in (None, k):
-                raise ValueError(f"{name}: {k} seeds do not match {na}")
-            na = k
-            if ld and a.shape[0] != B:
-                raise ValueError(f"{name}: batch size {a.shape[0]} does not match {B}")
-            ins.append((a, ld))
+        seeds, na, _ = self._host_seeds((("x_bar", x_bar, self.nw), ("lam_g_bar", lam_g_bar, self.ng),
+                                         ("X_bar", X_bar, self.nX)), B, "seeds", grow=False)
         if na is None:
             raise ValueError("x_bar, lam_g_bar or X_bar is required")
+        ins += seeds
         out = {"pbar": np.empty((B, na, self.np)), "q": np.empty((B, na, self.nw)), "jq": np.empty((B, na, self.ng))}
         info, delta = np.empty(B, dtype=np.int32), np.empty(B)
         _lib.check(_lib.lib().nmpc_solve_adjoint_batch(
-            self._h, B, na, *self._flat_ins(ins), _dptr(out["pbar"]), _dptr(out["q"]), _dptr(out["jq"]),
+            self._h, B, na, *_flat_ins(ins), _dptr(out["pbar"]), _dptr(out["q"]), _dptr(out["jq"]),
             info.ctypes.data_as(_IP), _dptr(delta)))
         self._raise_equality_rows(info, lbg, ubg, "sensitivity_adjoint_fused")
         res = {k: np.ascontiguousarray(t.transpose(2, 1, 0)) for k, t in out.items()}
@@ -1105,31 +836,17 @@ class Solver:
         delta ladder factorises; -11: an equality row, lbx > ubx or a NaN multiplier) has NaN in
         pbar, q and jq.  Enqueued on ``stream`` (default = current); never synchronises the host
         and reads nothing back."""
-        import torch  # plumbing only: device memory and streams
-
-        given = [out[k] for k in ("pbar", "q") if out.get(k) is not None]
-        if not given:
+        if out.get("pbar") is None and out.get("q") is None:
             raise ValueError("sensitivity_adjoint_device: out holds neither pbar nor q")
         if x_bar is None and lam_g_bar is None and X_bar is None:
             raise ValueError("x_bar, lam_g_bar or X_bar is required")
-        B, na = given[0].shape[0], given[0].shape[1]
-
-        def sv(t, n, name):
-            if t is None:
-                return C.c_void_p(0), 0
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), name
-            assert tuple(t.shape) in ((na, n), (B, na, n)), (name, tuple(t.shape))
-            return C.c_void_p(t.data_ptr()), (0 if t.dim() == 2 else na * n)
-
+        B, na = _first_out(out, ("pbar", "q"), "sensitivity_adjoint_device").shape[:2]
         ins, _ = self._point_ins_device(sol, lbx, ubx, lbg, ubg, p, B)
-        ins += (list(sv(x_bar, self.nw, "x_bar")) + list(sv(lam_g_bar, self.ng, "lam_g_bar"))
-                + list(sv(X_bar, self.nX, "X_bar")))
-        outs = self._out_ptrs_device(out, (("pbar", (B, na, self.np)), ("q", (B, na, self.nw)),
-                                           ("jq", (B, na, self.ng)), ("info", (B,)), ("delta", (B,))))
-        if stream is None:
-            stream = torch.cuda.current_stream()
-        _lib.check(_lib.lib().nmpc_solve_adjoint_batch_dev(self._h, B, na, *ins, *outs,
-                                                           C.c_void_p(stream.cuda_stream)))
+        ins += _dev_ins((("x_bar", x_bar, (na, self.nw)), ("lam_g_bar", lam_g_bar, (na, self.ng)),
+                         ("X_bar", X_bar, (na, self.nX))), B)
+        outs = _dev_outs(out, (("pbar", (B, na, self.np)), ("q", (B, na, self.nw)), ("jq", (B, na, self.ng)),
+                               ("info", (B,)), ("delta", (B,))))
+        _lib.check(_lib.lib().nmpc_solve_adjoint_batch_dev(self._h, B, na, *ins, *outs, _stream_ptr(stream)))
 
     # ---- forward mode in one launch (nmpc_solve_tangent_batch: weights, ladder, parameter
     # products, solves)
@@ -1144,11 +861,11 @@ class Solver:
         ``ValueError``, as :meth:`barrier_weights` does."""
         d, nd = self._dp_dirs(dp, 1)
         ins, B = self._point_ins_host(sol, lbx, ubx, lbg, ubg, p)
-        ins.append(self._dp_arg(d, B))
+        ins.append(self._dp_arg(d, B)[0])
         out = {"dx": np.empty((B, nd, self.nw)), "dlam_g": np.empty((B, nd, self.ng)), "dX": np.empty((B, nd, self.nX))}
         info, delta = np.empty(B, dtype=np.int32), np.empty(B)
         _lib.check(_lib.lib().nmpc_solve_tangent_batch(
-            self._h, B, nd, *self._flat_ins(ins), _dptr(out["dx"]), _dptr(out["dlam_g"]), _dptr(out["dX"]),
+            self._h, B, nd, *_flat_ins(ins), _dptr(out["dx"]), _dptr(out["dlam_g"]), _dptr(out["dX"]),
             info.ctypes.data_as(_IP), _dptr(delta)))
         self._raise_equality_rows(info, lbg, ubg, "sensitivity_fused")
         res = {k: np.ascontiguousarray(t.transpose(2, 1, 0)) for k, t in out.items()}
@@ -1164,22 +881,14 @@ class Solver:
         scenario whose ``info`` is not 0 (1: no rung of the delta ladder factorises; -11: an
         equality row, lbx > ubx or a NaN multiplier) has NaN in dx, dlam_g and dX.  Enqueued on
         ``stream`` (default = current); never synchronises the host and reads nothing back."""
-        import torch  # plumbing only: device memory and streams
-
-        given = [out[k] for k in ("dx", "dlam_g", "dX") if out.get(k) is not None]
-        if not given:
-            raise ValueError("sensitivity_device: out holds none of dx, dlam_g, dX")
+        B, nd = _first_out(out, ("dx", "dlam_g", "dX"), "sensitivity_device").shape[:2]
         if dp is None:
             raise ValueError("dp is required")
-        B, nd = given[0].shape[0], given[0].shape[1]
         ins, _ = self._point_ins_device(sol, lbx, ubx, lbg, ubg, p, B)
-        ins += self._dp_device(dp, nd, B)
-        outs = self._out_ptrs_device(out, (("dx", (B, nd, self.nw)), ("dlam_g", (B, nd, self.ng)),
-                                           ("dX", (B, nd, self.nX)), ("info", (B,)), ("delta", (B,))))
-        if stream is None:
-            stream = torch.cuda.current_stream()
-        _lib.check(_lib.lib().nmpc_solve_tangent_batch_dev(self._h, B, nd, *ins, *outs,
-                                                           C.c_void_p(stream.cuda_stream)))
+        ins += _dev_in(dp, (nd, self.np), B, "dp")
+        outs = _dev_outs(out, (("dx", (B, nd, self.nw)), ("dlam_g", (B, nd, self.ng)), ("dX", (B, nd, self.nX)),
+                               ("info", (B,)), ("delta", (B,))))
+        _lib.check(_lib.lib().nmpc_solve_tangent_batch_dev(self._h, B, nd, *ins, *outs, _stream_ptr(stream)))
 
     def feedback_gain_device(self, sol: dict, lbx, ubx, lbg, ubg, p, out: dict | None = None, stream=None):
         """Returns ``(K, info)``: the NMPC law's feedback gain K = d u0* / d x0, (B, nu, nx), and
@@ -1228,13 +937,13 @@ class Solver:
         if nd == 0:
             d = None
         ins, B = self._point_ins_host(sol, lbx, ubx, lbg, ubg, p)
-        ins.append((None, 0) if d is None else self._dp_arg(d, B))
+        ins.append((None, 0) if d is None else self._dp_arg(d, B)[0])
         K, A, Bm = np.empty((B, N, nx, nu)), np.empty((B, N, nx, nx)), np.empty((B, N, nu, nx))
         kff = np.empty((B, nd, N, nu)) if nd else None
         X = np.empty((B, N + 1, nx))
         info, delta = np.empty(B, dtype=np.int32), np.empty(B)
         _lib.check(_lib.lib().nmpc_solve_policy_batch(
-            self._h, B, nd, *self._flat_ins(ins), _dptr(K), _dptr(kff) if nd else None, _dptr(A), _dptr(Bm),
+            self._h, B, nd, *_flat_ins(ins), _dptr(K), _dptr(kff) if nd else None, _dptr(A), _dptr(Bm),
             _dptr(X), info.ctypes.data_as(_IP), _dptr(delta)))
         self._raise_equality_rows(info, lbg, ubg, "policy_fused")
         # the blocks are column-major: K_k is stored (nx, nu), A_k (nx, nx), B_k (nu, nx)
@@ -1259,7 +968,7 @@ class Solver:
         ins, B = self._point_ins_device(sol, lbx, ubx, lbg, ubg, p)
         x = sol["x"]
         nd = 0 if dp is None else dp.shape[-2]
-        ins += self._dp_device(dp, nd, B) if nd else [C.c_void_p(0), 0]
+        ins += _dev_in(dp if nd else None, (nd, self.np), B, "dp")
         if stream is None:
             stream = torch.cuda.current_stream()
         shapes = {"K": (B, N, nx, nu), "kff": (B, nd, N, nu), "A": (B, N, nx, nx), "B": (B, N, nu, nx),
@@ -1267,18 +976,13 @@ class Solver:
         raw = {}
         with torch.cuda.stream(stream):
             for k, shp in shapes.items():
+                raw[k] = (out or {}).get(k)
                 if k == "kff" and nd == 0:
                     raw[k] = None
-                    continue
-                dt = torch.int32 if k == "info" else torch.float64
-                t = (out or {}).get(k)
-                if t is not None:
-                    assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp, k
-                else:
-                    t = torch.empty(shp, dtype=dt, device=x.device)
-                raw[k] = t
-        ptr = [C.c_void_p(raw[k].data_ptr()) if raw[k] is not None else C.c_void_p(0) for k in shapes]
-        _lib.check(_lib.lib().nmpc_solve_policy_batch_dev(self._h, B, nd, *ins, *ptr, C.c_void_p(stream.cuda_stream)))
+                elif raw[k] is None:
+                    raw[k] = torch.empty(shp, dtype=torch.int32 if k == "info" else torch.float64, device=x.device)
+        ptr = _dev_outs(raw, shapes.items())
+        _lib.check(_lib.lib().nmpc_solve_policy_batch_dev(self._h, B, nd, *ins, *ptr, _stream_ptr(stream)))
         return {"K": raw["K"].transpose(2, 3), "kff": raw["kff"], "A": raw["A"].transpose(2, 3),
                 "B": raw["B"].transpose(2, 3), "X": raw["X"], "info": raw["info"], "delta": raw["delta"], "raw": raw}
 
@@ -1308,10 +1012,6 @@ class Solver:
 
         N, nu, nx = self._policy_dims()
 
-        def chk(t, name):
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), name
-
-        chk(e0, "e0")
         assert e0.dim() in (2, 3) and e0.shape[-1] == nx, ("e0", tuple(e0.shape))
         M = e0.shape[-2]
         B = None
@@ -1322,44 +1022,29 @@ class Solver:
         if B is None:
             raise ValueError("policy_rollout_device: no argument carries the batch size")
 
-        def dv(t, tail, name):
-            """(pointer, ld) of a (B, *tail) tensor, or of a shared one of shape tail."""
-            if t is None:
-                return [C.c_void_p(0), 0]
-            chk(t, name)
-            n = int(np.prod(tail))
-            if tuple(t.shape) == tuple(tail):
-                return [C.c_void_p(t.data_ptr()), 0]
-            assert tuple(t.shape) == (B, *tail), (name, tuple(t.shape), (B, *tail))
-            return [C.c_void_p(t.data_ptr()), n]
-
         if K is not None and tuple(K.shape[-2:]) == (nu, nx):
             K = K.transpose(-1, -2)  # policy_device's view back to the kernel's column-major blocks
         if p is None or ubar is None or Xbar is None:
             raise ValueError("p, ubar and Xbar are required")
         if (lbg is None) != (ubg is None):
             raise ValueError("lbg and ubg must be given together")
-        ins = (dv(p, (self.np,), "p") + dv(ubar, (self.nw,), "ubar") + dv(Xbar, (N + 1, nx), "Xbar")
-               + dv(K, (N, nx, nu), "K") + dv(lbx, (self.nw,), "lbx") + dv(ubx, (self.nw,), "ubx")
-               + dv(lbg, (self.ng,), "lbg") + dv(ubg, (self.ng,), "ubg") + dv(e0, (M, nx), "e0")
-               + dv(w, (M, N, nx), "w"))
+        ins = _dev_ins((("p", p, (self.np,)), ("ubar", ubar, (self.nw,)), ("Xbar", Xbar, (N + 1, nx)),
+                        ("K", K, (N, nx, nu)), ("lbx", lbx, (self.nw,)), ("ubx", ubx, (self.nw,)),
+                        ("lbg", lbg, (self.ng,)), ("ubg", ubg, (self.ng,)), ("e0", e0, (M, nx)),
+                        ("w", w, (M, N, nx))), B)
         if stream is None:
             stream = torch.cuda.current_stream()
         shapes = self._rollout_shapes(B, M)
-        res = {}
+        res = dict(out or {})
         with torch.cuda.stream(stream):
-            for k in self.ROLLOUT_OUT:
-                t = (out or {}).get(k)
-                dt = torch.int32 if k == "nsat" else torch.float64
-                if t is not None:
-                    assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shapes[k], k
-                elif k in want:
-                    t = torch.empty(shapes[k], dtype=dt, device=e0.device)
-                res[k] = t
-        if all(res[k] is None for k in ("J", "viol", "X", "U")):
+            for k in want:
+                if res.get(k) is None:
+                    res[k] = torch.empty(shapes[k], dtype=torch.int32 if k == "nsat" else torch.float64,
+                                         device=e0.device)
+        if all(res.get(k) is None for k in ("J", "viol", "X", "U")):
             raise ValueError("policy_rollout_device: one of J, viol, X, U is required")
-        ptr = [C.c_void_p(res[k].data_ptr()) if res[k] is not None else C.c_void_p(0) for k in self.ROLLOUT_OUT]
-        _lib.check(_lib.lib().nmpc_policy_rollout_batch_dev(self._h, B, M, *ins, *ptr, C.c_void_p(stream.cuda_stream)))
+        ptr = _dev_outs(res, shapes.items())
+        _lib.check(_lib.lib().nmpc_policy_rollout_batch_dev(self._h, B, M, *ins, *ptr, _stream_ptr(stream)))
         return {k: v for k, v in res.items() if v is not None}
 
     def policy_rollout(self, p, ubar, Xbar, K, e0, w=None, lbx=None, ubx=None, lbg=None, ubg=None,
@@ -1408,7 +1093,7 @@ class Solver:
             raise ValueError("policy_rollout: one of J, viol, X, U is required")
         ptr = [None if k not in res else (res[k].ctypes.data_as(_IP) if k == "nsat" else _dptr(res[k]))
                for k in self.ROLLOUT_OUT]
-        _lib.check(_lib.lib().nmpc_policy_rollout_batch(self._h, B, M, *self._flat_ins(arrs), *ptr))
+        _lib.check(_lib.lib().nmpc_policy_rollout_batch(self._h, B, M, *_flat_ins(arrs), *ptr))
         return res
 
     def shift_device(self, p, u_sol, w_out, v_t, w_t, stream=None):
@@ -1449,18 +1134,8 @@ class Solver:
         L = _lib.lib()
         B = w.shape[0]
         hist = hist or {}
-
-        def dv(t, n):
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous()
-            if t.dim() == 1:
-                assert t.shape[0] == n
-                return C.c_void_p(t.data_ptr()), 0
-            assert t.shape == (B, n), (tuple(t.shape), (B, n))
-            return C.c_void_p(t.data_ptr()), n
-
-        ins = []
-        for t, n in ((lbx, self.nw), (ubx, self.nw), (lbg, self.ng), (ubg, self.ng)):
-            ins += list(dv(t, n))
+        ins = _dev_ins((("lbx", lbx, (self.nw,)), ("ubx", ubx, (self.nw,)), ("lbg", lbg, (self.ng,)),
+                        ("ubg", ubg, (self.ng,))), B)
         assert p.shape == (B, self.np) and p.is_contiguous() and p.dtype == torch.float64
         assert w.shape == (B, self.nw) and w.is_contiguous() and w.dtype == torch.float64
         assert v_t.shape == w_t.shape and v_t.dtype == torch.float64 and w_t.dtype == torch.float64

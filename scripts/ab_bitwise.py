@@ -10,7 +10,9 @@ With --fused before the file name the dump is every output of the three entry po
 point (sensitivity_adjoint_fused, sensitivity_fused, policy_fused) and of kkt_solve instead: on
 the solved cases of tests/solve_adjoint_ref.py (na = 3 seeds of all three kinds, nd = 3
 directions), and on one batch per exit of the kernels -- fixed controls, info = -11, and info = 1
-with the ladder exhausted.  The points themselves are dumped too, so equal inputs are shown, and
+with the ladder exhausted.  On the solved cases it also dumps evaluate, products, param_products,
+adjoint_products and policy_rollout (5 samples), each through the host entry point and through the
+device one, so every batched entry point is covered.  The points themselves are dumped too, so equal inputs are shown, and
 --compare takes NaNs in the same places as equal whatever their payloads.
 """
 import os, sys
@@ -37,6 +39,8 @@ def compare(a, b):
 
 def fused(path):
     sys.path.insert(0, ROOT)
+    import torch  # before the library, as main() and the tests have it: the device paths need it
+    torch.cuda.init()
     from nmpc_amd import nlpsol, REFERENCE_OPTS
     from tests import solve_adjoint_ref as sr
 
@@ -57,7 +61,56 @@ def fused(path):
                 out[f"{tag}_{name}_{k}"] = np.asarray(v)
         print(tag, "info", out[f"{tag}_adj_info"], out[f"{tag}_tan_info"], out[f"{tag}_pol_info"], "delta",
               out[f"{tag}_tan_delta"])
-        return sd
+        return sd, dp
+
+    def given_points(tag, s, sol, bounds, P, B, spec, sd, dp):
+        """evaluate, products, param_products, adjoint_products and policy_rollout at the point, each
+        through the host entry point and through the device one."""
+        import torch
+
+        def t(a):
+            return torch.tensor(np.ascontiguousarray(a), dtype=torch.float64, device="cuda")
+
+        def bm(a):  # (n, k, B) -> the device layout (B, k, n)
+            return t(np.transpose(a, (2, 1, 0)))
+
+        def empty(**shapes):
+            return {k: torch.empty(shp, dtype=torch.int32 if k == "nsat" else torch.float64, device="cuda")
+                    for k, shp in shapes.items()}
+
+        nw, ng, npp, nX, N = spec.nw, spec.ng, spec.np, spec.nX, spec.N
+        nu, nx = nw // N, nX // (N + 1)
+        x, lg, lx = sol["x"], sol["lam_g"], sol["lam_x"]
+        dx, dP, dlg, dlx = t(x.T), t(P), t(lg.T), t(lx.T)
+        db = [t(v) for v in bounds]
+        pol = s.policy_fused(sol, *bounds, P.T)
+        rng = np.random.default_rng(7)
+        e0, w = 0.05 * rng.standard_normal((B, 5, nx)), 0.005 * rng.standard_normal((B, 5, N, nx))
+        host = {"ev": s.evaluate(x, P.T, lam_g=lg, lam_x=lx, lbx=bounds[0], ubx=bounds[1], lbg=bounds[2], ubg=bounds[3]),
+                "prod": s.products(x, P.T, sd["x_bar"], lam_g=lg, obj_factor=0.7),
+                "pprod": s.param_products(x, P.T, dp, lam_g=lg, obj_factor=0.7),
+                "adjp": s.adjoint_products(x, P.T, y=sd["lam_g_bar"], z=sd["x_bar"], Xbar=sd["X_bar"], lam_g=lg,
+                                           obj_factor=0.7),
+                "roll": s.policy_rollout(P, x.T, pol["X"], pol["K"], e0, w=w, lbx=bounds[0], ubx=bounds[1],
+                                         lbg=bounds[2], ubg=bounds[3])}
+        dev = {"ev": empty(f=(B,), g=(B, ng), X=(B, nX), grad_f=(B, nw), grad_l=(B, nw), kkt=(B, 5)),
+               "prod": empty(jv=(B, 3, ng), hv=(B, 3, nw), dX=(B, 3, nX)),
+               "pprod": empty(jp=(B, 3, ng), hp=(B, 3, nw), dXp=(B, 3, nX), gp=(B, npp)),
+               "adjp": empty(wbar=(B, 3, nw), pbar=(B, 3, npp))}
+        s.evaluate_device(dx, dP, dev["ev"], lam_g=dlg, lam_x=dlx, lbx=db[0], ubx=db[1], lbg=db[2], ubg=db[3])
+        s.products_device(dx, dP, bm(sd["x_bar"]), dev["prod"], lam_g=dlg, obj_factor=0.7)
+        s.param_products_device(dx, dP, bm(dp), dev["pprod"], lam_g=dlg, obj_factor=0.7)
+        s.adjoint_products_device(dx, dP, dev["adjp"], y=bm(sd["lam_g_bar"]), z=bm(sd["x_bar"]), Xbar=bm(sd["X_bar"]),
+                                  lam_g=dlg, obj_factor=0.7)
+        Kraw = t(np.swapaxes(pol["K"], -1, -2))  # the kernel's column-major blocks
+        dev["roll"] = s.policy_rollout_device(dP, dx, t(pol["X"]), Kraw, t(e0), w=t(w), lbx=db[0], ubx=db[1],
+                                              lbg=db[2], ubg=db[3], want=("J", "viol", "nsat", "X", "U"))
+        torch.cuda.synchronize()
+        for name in host:
+            for k, v in host[name].items():
+                out[f"{tag}_{name}_{k}"] = np.asarray(v)
+            for k, v in dev[name].items():
+                out[f"{tag}_{name}_dev_{k}"] = v.cpu().numpy()
 
     for name, (B, _) in sr.SOLVED.items():
         spec, P = sr.scenarios(name)
@@ -67,7 +120,8 @@ def fused(path):
         sol = {k: np.array(sol[k], dtype=np.float64).reshape(-1, B) for k in ("x", "g", "lam_x", "lam_g")}
         for k, v in sol.items():
             out[f"{name}_point_{k}"] = v
-        sd = dump(name, s, sol, bounds, P, B, spec, 1)
+        sd, dp = dump(name, s, sol, bounds, P, B, spec, 1)
+        given_points(name, s, sol, bounds, P, B, spec, sd, dp)
         # the KKT solves at the point's weights, at delta = 0 and at a delta every case factorises with
         sx, ss = s.barrier_weights(sol, *bounds)
         for dl in (0.0, 1e-4):

@@ -303,18 +303,28 @@ def test_argument_validation_on_a_live_handle():
                 g(wbar), g(pbar)]
         return L.nmpc_adjoint_products_batch_dev(*args, vp(0)) if dev else L.nmpc_adjoint_products_batch(*args)
 
+    # each with the full message of its rule; the last three break two rules at once: the earlier
+    # one in the order of the checks answers
+    req, ldm = "required pointer is null (x, p)", "leading dimension smaller than the vector length"
+    seeds, outs = "every seed pointer is null (y, z, Xb)", "every output pointer is null (wbar, pbar)"
     for dev in (False, True):
-        for what, kw in (("B = 0", dict(B_=0)), ("B < 0", dict(B_=-3)), ("na = 0", dict(na_=0)),
-                         ("na < 0", dict(na_=-1)), ("x NULL", dict(x=None)), ("p NULL", dict(p=None)),
-                         ("every seed NULL", dict(y=None, z=None, Xb=None)),
-                         ("both outputs NULL", dict(wbar=None, pbar=None)),
-                         ("ld_x short", dict(ld_x=nw - 1)), ("ld_p short", dict(ld_p=npp - 1)),
-                         ("ld_lam_g short", dict(ld_lam=ng - 1)), ("ld_y short", dict(ld_y=ng * na - 1)),
-                         ("ld_y one seed", dict(ld_y=ng)), ("ld_z short", dict(ld_z=nw * na - 1)),
-                         ("ld_Xb short", dict(ld_Xb=nX * na - 1)), ("ld_x negative", dict(ld_x=-nw))):
+        for what, kw, msg in (("B = 0", dict(B_=0), "B <= 0"), ("B < 0", dict(B_=-3), "B <= 0"),
+                              ("na = 0", dict(na_=0), "na <= 0"), ("na < 0", dict(na_=-1), "na <= 0"),
+                              ("x NULL", dict(x=None), req), ("p NULL", dict(p=None), req),
+                              ("every seed NULL", dict(y=None, z=None, Xb=None), seeds),
+                              ("both outputs NULL", dict(wbar=None, pbar=None), outs),
+                              ("ld_x short", dict(ld_x=nw - 1), ldm), ("ld_p short", dict(ld_p=npp - 1), ldm),
+                              ("ld_lam_g short", dict(ld_lam=ng - 1), ldm), ("ld_y short", dict(ld_y=ng * na - 1), ldm),
+                              ("ld_y one seed", dict(ld_y=ng), ldm), ("ld_z short", dict(ld_z=nw * na - 1), ldm),
+                              ("ld_Xb short", dict(ld_Xb=nX * na - 1), ldm), ("ld_x negative", dict(ld_x=-nw), ldm),
+                              ("B = 0 and na = 0", dict(B_=0, na_=0), "B <= 0"),
+                              ("na = 0 and x NULL", dict(na_=0, x=None), "na <= 0"),
+                              ("no seed and no output", dict(y=None, z=None, Xb=None, wbar=None, pbar=None), seeds),
+                              ("no output and ld_x short", dict(wbar=None, pbar=None, ld_x=nw - 1), outs)):
             rc = call(dev=dev, **kw)
             assert rc == -1, (what, dev, rc)  # NMPC_E_INVALID
             assert L.nmpc_last_error(), what
+            assert L.nmpc_last_error().decode() == msg, (what, dev)
     call(y=None, z=None, Xb=None)
     assert "seed" in L.nmpc_last_error().decode()
     call(wbar=None, pbar=None)

@@ -112,13 +112,36 @@ def test_argument_validation_on_a_live_handle():
     ptr = lambda a: a.ctypes.data_as(dp)  # noqa: E731
     bnd = [ptr(d[k]) for k in ("lbx", "ubx", "lbg", "ubg")]
 
-    def call(B, bounds, outs):
-        ins = [ptr(w), spec.nw, ptr(p), spec.np, None, 0, None, 0]
+    def call(B, bounds, outs, dev=False, x=ptr(w), ld_x=spec.nw, h=s._h):
+        ins = [x, ld_x, ptr(p), spec.np, None, 0, None, 0]
         for q in bounds:
             ins += [q, 0]
-        return L.nmpc_eval_batch(s._h, B, *ins, *outs)
+        if dev:  # the checks return before anything reads a pointer
+            return L.nmpc_eval_batch_dev(h, B, *ins, *outs, None)
+        return L.nmpc_eval_batch(h, B, *ins, *outs)
 
     none6 = [None] * 6
+    # the full message of every rule, on both entry points; the last four break two rules at
+    # once: the earlier one in the order of the checks answers
+    f1, k1 = [ptr(f)] + none6[1:], none6[:5] + [ptr(kkt)]
+    for dev in (False, True):
+        for what, kw, msg in (
+                ("null handle", dict(B=2, bounds=bnd, outs=f1, h=None), "null handle"),
+                ("B = 0", dict(B=0, bounds=bnd, outs=f1), "B <= 0"),
+                ("x NULL", dict(B=2, bounds=bnd, outs=f1, x=None), "required pointer is null (x, p)"),
+                ("no output", dict(B=2, bounds=bnd, outs=none6), "every output pointer is null"),
+                ("kkt without ubg", dict(B=2, bounds=bnd[:3] + [None], outs=k1),
+                 "kkt_out needs lbx, ubx, lbg and ubg"),
+                ("ld_x short", dict(B=2, bounds=bnd, outs=f1, ld_x=spec.nw - 1),
+                 "leading dimension smaller than the vector length"),
+                ("null handle and B = 0", dict(B=0, bounds=bnd, outs=f1, h=None), "null handle"),
+                ("B = 0 and x NULL", dict(B=0, bounds=bnd, outs=f1, x=None), "B <= 0"),
+                ("x NULL and no output", dict(B=2, bounds=bnd, outs=none6, x=None),
+                 "required pointer is null (x, p)"),
+                ("kkt without ubg and ld_x short", dict(B=2, bounds=bnd[:3] + [None], outs=k1, ld_x=spec.nw - 1),
+                 "kkt_out needs lbx, ubx, lbg and ubg")):
+            assert call(dev=dev, **kw) == -1, (what, dev)
+            assert L.nmpc_last_error().decode() == msg, (what, dev)
     for what, rc in (("B = 0", call(0, bnd, [ptr(f)] + none6[1:])), ("B < 0", call(-3, bnd, [ptr(f)] + none6[1:])),
                      ("no output", call(2, bnd, none6)),
                      ("kkt without ubg", call(2, bnd[:3] + [None], none6[:5] + [ptr(kkt)])),

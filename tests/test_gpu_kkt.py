@@ -302,9 +302,31 @@ def test_argument_validation_on_a_live_handle():
     nw, ng = spec.nw, spec.ng
 
     def call(B_=B, nr_=nr, x=ptr(w), ld_x=nw, p_=ptr(p), ld_p=spec.np, lam=ptr(lg), ld_lam=ng, sx_=ptr(sx), ld_sx=nw,
-             ss_=ptr(ss), ld_ss=ng, dl_=ptr(dl), ld_dl=1, rw_=ptr(rw), ld_rw=nw * nr, rg_=ptr(rg), ld_rg=ng * nr, o=outs):
-        return L.nmpc_kkt_solve_batch(s._h, B_, nr_, x, ld_x, p_, ld_p, lam, ld_lam, 1.0, sx_, ld_sx, ss_, ld_ss, dl_,
-                                      ld_dl, rw_, ld_rw, rg_, ld_rg, *o, info.ctypes.data_as(C.POINTER(C.c_int32)))
+             ss_=ptr(ss), ld_ss=ng, dl_=ptr(dl), ld_dl=1, rw_=ptr(rw), ld_rw=nw * nr, rg_=ptr(rg), ld_rg=ng * nr, o=outs,
+             dev=False, h=s._h):
+        a = (h, B_, nr_, x, ld_x, p_, ld_p, lam, ld_lam, 1.0, sx_, ld_sx, ss_, ld_ss, dl_, ld_dl, rw_, ld_rw, rg_,
+             ld_rg, *o, info.ctypes.data_as(C.POINTER(C.c_int32)))
+        # on the device entry point the checks return before anything reads a pointer
+        return L.nmpc_kkt_solve_batch_dev(*a, None) if dev else L.nmpc_kkt_solve_batch(*a)
+
+    # the full message of every rule, on both entry points; the last four break two rules at
+    # once: the earlier one in the order of the checks answers
+    for dev in (False, True):
+        for what, kw, msg in (
+                ("null handle", dict(h=None), "null handle"), ("B = 0", dict(B_=0), "B <= 0"),
+                ("nr = 0", dict(nr_=0), "nr <= 0"), ("p NULL", dict(p_=None), "required pointer is null (x, p)"),
+                ("both right-hand sides NULL", dict(rw_=None, rg_=None), "both right-hand sides are null (r_w, r_g)"),
+                ("no output", dict(o=[None] * 3), "every output pointer is null (dw, dX, jdw)"),
+                ("ld_r_g short", dict(ld_rg=ng * nr - 1), "leading dimension smaller than the vector length"),
+                ("ld_delta negative", dict(ld_dl=-1), "leading dimension smaller than the vector length"),
+                ("B = 0 and nr = 0", dict(B_=0, nr_=0), "B <= 0"),
+                ("nr = 0 and x NULL", dict(nr_=0, x=None), "nr <= 0"),
+                ("no right-hand side and no output", dict(rw_=None, rg_=None, o=[None] * 3),
+                 "both right-hand sides are null (r_w, r_g)"),
+                ("no output and ld_x short", dict(o=[None] * 3, ld_x=nw - 1),
+                 "every output pointer is null (dw, dX, jdw)")):
+            assert call(dev=dev, **kw) == -1, (what, dev)
+            assert L.nmpc_last_error().decode() == msg, (what, dev)
 
     for what, rc in (("B = 0", call(B_=0)), ("B < 0", call(B_=-3)), ("nr = 0", call(nr_=0)), ("nr < 0", call(nr_=-1)),
                      ("x NULL", call(x=None)), ("p NULL", call(p_=None)), ("both right-hand sides NULL", call(rw_=None, rg_=None)),

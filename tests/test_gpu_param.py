@@ -289,10 +289,31 @@ def test_argument_validation_on_a_live_handle():
     outs = [ptr(out[k]) for k in KEYS]
 
     def call(B_=B, nd_=nd, x=ptr(w), ld_x=spec.nw, p_=ptr(p), ld_p=spec.np, lam=ptr(lg), ld_lam=spec.ng, d_=ptr(dp),
-             ld_dp=spec.np * nd, o=outs):
-        return L.nmpc_param_products_batch(s._h, B_, nd_, x, ld_x, p_, ld_p, lam, ld_lam, 1.0, d_, ld_dp, *o)
+             ld_dp=spec.np * nd, o=outs, dev=False, h=s._h):
+        a = (h, B_, nd_, x, ld_x, p_, ld_p, lam, ld_lam, 1.0, d_, ld_dp, *o)
+        # on the device entry point the checks return before anything reads a pointer
+        return L.nmpc_param_products_batch_dev(*a, None) if dev else L.nmpc_param_products_batch(*a)
 
     gp_only = [None, None, None, outs[3]]
+    # the full message of every rule, on both entry points; the last four break two rules at
+    # once: the earlier one in the order of the checks answers
+    nd0 = "nd = 0 takes gp_out alone (dp and the directional outputs must be null)"
+    for dev in (False, True):
+        for what, kw, msg in (
+                ("null handle", dict(h=None), "null handle"), ("B = 0", dict(B_=0), "B <= 0"),
+                ("nd < 0", dict(nd_=-1), "nd < 0"), ("x NULL", dict(x=None), "required pointer is null (x, p)"),
+                ("no output", dict(o=[None] * 4), "every output pointer is null"),
+                ("hp with nd = 0", dict(nd_=0, d_=None, o=[None, outs[1], None, None]), nd0),
+                ("dp with nd = 0", dict(nd_=0, o=gp_only), nd0),
+                ("directional output, dp NULL", dict(d_=None), "required pointer is null (dp with nd > 0)"),
+                ("ld_dp short", dict(ld_dp=spec.np * nd - 1), "leading dimension smaller than the vector length"),
+                ("B = 0 and nd < 0", dict(B_=0, nd_=-1), "B <= 0"),
+                ("nd < 0 and p NULL", dict(nd_=-1, p_=None), "nd < 0"),
+                ("no output and dp NULL", dict(o=[None] * 4, d_=None), "every output pointer is null"),
+                ("dp NULL and ld_x short", dict(d_=None, ld_x=spec.nw - 1),
+                 "required pointer is null (dp with nd > 0)")):
+            assert call(dev=dev, **kw) == -1, (what, dev)
+            assert L.nmpc_last_error().decode() == msg, (what, dev)
     for what, rc in (("B = 0", call(B_=0)), ("B < 0", call(B_=-3)), ("nd < 0", call(nd_=-1)),
                      ("x NULL", call(x=None)), ("p NULL", call(p_=None)), ("no output", call(o=[None] * 4)),
                      ("jp with nd = 0", call(nd_=0, d_=None, o=[outs[0], None, None, outs[3]])),

@@ -408,17 +408,26 @@ def test_argument_validation_on_a_live_handle():
         args += [g(k) for k in OUT] + [gi, g("delta")]
         return L.nmpc_solve_policy_batch_dev(*args, vp(0)) if dev else L.nmpc_solve_policy_batch(*args)
 
+    # each with the full message of its rule; the last four break two rules at once: the earlier
+    # one in the order of the checks answers
+    req, ldm = "required pointer is null (x, p, lam_g, lam_x, lbx, ubx, lbg, ubg)", "leading dimension smaller than the vector length"
+    nd0, outs, nodp = "dp and kff_out must be null with nd = 0", "K_out, kff_out, A_out and B_out are all null", "dp is null with nd > 0"
     for dev in (False, True):
-        cases = [("B = 0", dict(B_=0)), ("B < 0", dict(B_=-3)), ("nd < 0", dict(nd_=-1)),
-                 ("nd = 0 with dp and kff", dict(nd_=0)), ("nd = 0 with dp", dict(nd_=0, null=("kff",))),
-                 ("nd = 0 with kff", dict(nd_=0, null=("dp",))), ("K, kff, A, B NULL", dict(null=MAIN)),
-                 ("ld_x negative", dict(ld={"x": -nw})), ("ld_dp one direction", dict(ld={"dp": npp}))]
-        cases += [(f"{k} NULL", dict(null=(k,))) for k in names if k != "g"]
-        cases += [(f"ld_{k} short", dict(ld={k: lens[k] - 1})) for k in names]
-        for what, kw in cases:
+        cases = [("B = 0", dict(B_=0), "B <= 0"), ("B < 0", dict(B_=-3), "B <= 0"), ("nd < 0", dict(nd_=-1), "nd < 0"),
+                 ("nd = 0 with dp and kff", dict(nd_=0), nd0), ("nd = 0 with dp", dict(nd_=0, null=("kff",)), nd0),
+                 ("nd = 0 with kff", dict(nd_=0, null=("dp",)), nd0), ("K, kff, A, B NULL", dict(null=MAIN), outs),
+                 ("ld_x negative", dict(ld={"x": -nw}), ldm), ("ld_dp one direction", dict(ld={"dp": npp}), ldm)]
+        cases += [(f"{k} NULL", dict(null=(k,)), nodp if k == "dp" else req) for k in names if k != "g"]
+        cases += [(f"ld_{k} short", dict(ld={k: lens[k] - 1}), ldm) for k in names]
+        cases += [("B = 0 and nd < 0", dict(B_=0, nd_=-1), "B <= 0"), ("nd < 0 and x NULL", dict(nd_=-1, null=("x",)), "nd < 0"),
+                  ("ubg NULL and dp NULL", dict(null=("ubg", "dp")), req),
+                  ("dp NULL and no output", dict(null=("dp",) + tuple(MAIN)), nodp),
+                  ("no output and ld_p short", dict(null=MAIN, ld={"p": npp - 1}), outs)]
+        for what, kw, msg in cases:
             rc = call(dev=dev, **kw)
             assert rc == -1, (what, dev, rc)  # NMPC_E_INVALID
             assert L.nmpc_last_error(), what
+            assert L.nmpc_last_error().decode() == msg, (what, dev)
     call(null=MAIN)
     assert "K_out" in L.nmpc_last_error().decode()
     with pytest.raises(_lib.NmpcError):

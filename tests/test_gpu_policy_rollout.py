@@ -394,17 +394,27 @@ def test_argument_validation_on_a_live_handle():
         return L.nmpc_policy_rollout_batch_dev(*args, vp(0)) if dev else L.nmpc_policy_rollout_batch(*args)
 
     main = ("J", "viol", "X", "U")
+    # each with the full message of its rule; the last five break two rules at once: the earlier
+    # one in the order of the checks answers
+    req, ldm = "required pointer is null (p, ubar, Xbar, e0)", "leading dimension smaller than the vector length"
+    outs, pair = "J_out, viol_out, X_out and U_out are all null", "lbg and ubg must be given together"
     for dev in (False, True):
-        cases = [("B = 0", dict(B_=0)), ("B < 0", dict(B_=-3)), ("M = 0", dict(M_=0)), ("M < 0", dict(M_=-1)),
-                 ("J, viol, X, U NULL", dict(null=main)), ("lbg without ubg", dict(null=("ubg",))),
-                 ("ubg without lbg", dict(null=("lbg",))), ("ld_p negative", dict(ld={"p": -spec.np})),
-                 ("ld_e0 one sample", dict(ld={"e0": nx}))]
-        cases += [(f"{k} NULL", dict(null=(k,))) for k in ("p", "ubar", "Xbar", "e0")]
-        cases += [(f"ld_{k} short", dict(ld={k: lens[k] - 1})) for k in names]
-        for what, kw in cases:
+        cases = [("B = 0", dict(B_=0), "B <= 0"), ("B < 0", dict(B_=-3), "B <= 0"), ("M = 0", dict(M_=0), "M <= 0"),
+                 ("M < 0", dict(M_=-1), "M <= 0"), ("M too large", dict(M_=64 * 65535 + 1), "M > 64 x 65535"),
+                 ("J, viol, X, U NULL", dict(null=main), outs), ("lbg without ubg", dict(null=("ubg",)), pair),
+                 ("ubg without lbg", dict(null=("lbg",)), pair), ("ld_p negative", dict(ld={"p": -spec.np}), ldm),
+                 ("ld_e0 one sample", dict(ld={"e0": nx}), ldm)]
+        cases += [(f"{k} NULL", dict(null=(k,)), req) for k in ("p", "ubar", "Xbar", "e0")]
+        cases += [(f"ld_{k} short", dict(ld={k: lens[k] - 1}), ldm) for k in names]
+        cases += [("B = 0 and M = 0", dict(B_=0, M_=0), "B <= 0"), ("M = 0 and p NULL", dict(M_=0, null=("p",)), "M <= 0"),
+                  ("e0 NULL and no output", dict(null=("e0",) + main), req),
+                  ("no output and lbg without ubg", dict(null=main + ("ubg",)), outs),
+                  ("lbg without ubg and ld_w short", dict(null=("ubg",), ld={"w": lens["w"] - 1}), pair)]
+        for what, kw, msg in cases:
             rc = call(dev=dev, **kw)
             assert rc == -1, (what, dev, rc)  # NMPC_E_INVALID
             assert L.nmpc_last_error(), what
+            assert L.nmpc_last_error().decode() == msg, (what, dev)
     call(null=main)
     assert "J_out" in L.nmpc_last_error().decode()
     assert all(np.all(arr[k] == 7.0) for k in main) and np.all(nsat == 99)  # nothing ran

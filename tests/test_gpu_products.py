@@ -252,8 +252,26 @@ def test_argument_validation_on_a_live_handle():
     outs = [ptr(out[k]) for k in KEYS]
 
     def call(B_=B, nv_=nv, x=ptr(w), ld_x=spec.nw, p_=ptr(p), ld_p=spec.np, lam=ptr(lg), ld_lam=spec.ng, v_=ptr(v),
-             ld_v=spec.nw * nv, o=outs):
-        return L.nmpc_products_batch(s._h, B_, nv_, x, ld_x, p_, ld_p, lam, ld_lam, 1.0, v_, ld_v, *o)
+             ld_v=spec.nw * nv, o=outs, dev=False, h=s._h):
+        if dev:  # the checks return before anything reads a pointer
+            return L.nmpc_products_batch_dev(h, B_, nv_, x, ld_x, p_, ld_p, lam, ld_lam, 1.0, v_, ld_v, *o, None)
+        return L.nmpc_products_batch(h, B_, nv_, x, ld_x, p_, ld_p, lam, ld_lam, 1.0, v_, ld_v, *o)
+
+    # the full message of every rule, on both entry points; the last four break two rules at
+    # once: the earlier one in the order of the checks answers
+    for dev in (False, True):
+        for what, kw, msg in (
+                ("null handle", dict(h=None), "null handle"), ("B = 0", dict(B_=0), "B <= 0"),
+                ("nv = 0", dict(nv_=0), "nv <= 0"), ("v NULL", dict(v_=None), "required pointer is null (x, p, v)"),
+                ("x NULL", dict(x=None), "required pointer is null (x, p, v)"),
+                ("no output", dict(o=[None] * 3), "every output pointer is null"),
+                ("ld_v short", dict(ld_v=spec.nw * nv - 1), "leading dimension smaller than the vector length"),
+                ("B = 0 and nv = 0", dict(B_=0, nv_=0), "B <= 0"),
+                ("nv = 0 and p NULL", dict(nv_=0, p_=None), "nv <= 0"),
+                ("v NULL and no output", dict(v_=None, o=[None] * 3), "required pointer is null (x, p, v)"),
+                ("no output and ld_x short", dict(o=[None] * 3, ld_x=spec.nw - 1), "every output pointer is null")):
+            assert call(dev=dev, **kw) == -1, (what, dev)
+            assert L.nmpc_last_error().decode() == msg, (what, dev)
 
     for what, rc in (("B = 0", call(B_=0)), ("B < 0", call(B_=-3)), ("nv = 0", call(nv_=0)), ("nv < 0", call(nv_=-1)),
                      ("x NULL", call(x=None)), ("p NULL", call(p_=None)), ("v NULL", call(v_=None)),

@@ -507,17 +507,27 @@ def test_argument_validation_on_a_live_handle():
         args += [g("pbar"), g("q"), g("jq"), gi, g("delta")]
         return L.nmpc_solve_adjoint_batch_dev(*args, vp(0)) if dev else L.nmpc_solve_adjoint_batch(*args)
 
+    # each with the full message of its rule; the last four break two rules at once: the earlier
+    # one in the order of the checks answers
+    req, ldm = "required pointer is null (x, p, lam_g, lam_x, lbx, ubx, lbg, ubg)", "leading dimension smaller than the vector length"
+    seeds, outs = "every seed pointer is null (x_bar, lam_g_bar, X_bar)", "both pbar_out and q_out are null"
+    no_seed = ("x_bar", "lam_g_bar", "X_bar")
     for dev in (False, True):
-        cases = [("B = 0", dict(B_=0)), ("B < 0", dict(B_=-3)), ("na = 0", dict(na_=0)), ("na < 0", dict(na_=-1)),
-                 ("every seed NULL", dict(null=("x_bar", "lam_g_bar", "X_bar"))),
-                 ("pbar and q NULL", dict(null=("pbar", "q"))), ("ld_x negative", dict(ld={"x": -nw})),
-                 ("ld_x_bar one seed", dict(ld={"x_bar": nw}))]
-        cases += [(f"{k} NULL", dict(null=(k,))) for k in names[:9] if k != "g"]
-        cases += [(f"ld_{k} short", dict(ld={k: lens[k] - 1})) for k in names]
-        for what, kw in cases:
+        cases = [("B = 0", dict(B_=0), "B <= 0"), ("B < 0", dict(B_=-3), "B <= 0"), ("na = 0", dict(na_=0), "na <= 0"),
+                 ("na < 0", dict(na_=-1), "na <= 0"), ("every seed NULL", dict(null=no_seed), seeds),
+                 ("pbar and q NULL", dict(null=("pbar", "q")), outs), ("ld_x negative", dict(ld={"x": -nw}), ldm),
+                 ("ld_x_bar one seed", dict(ld={"x_bar": nw}), ldm)]
+        cases += [(f"{k} NULL", dict(null=(k,)), req) for k in names[:9] if k != "g"]
+        cases += [(f"ld_{k} short", dict(ld={k: lens[k] - 1}), ldm) for k in names]
+        cases += [("B = 0 and na = 0", dict(B_=0, na_=0), "B <= 0"), ("na = 0 and x NULL", dict(na_=0, null=("x",)), "na <= 0"),
+                  ("ubg NULL and no seed", dict(null=("ubg",) + no_seed), req),
+                  ("no seed and no output", dict(null=no_seed + ("pbar", "q")), seeds),
+                  ("no output and ld_p short", dict(null=("pbar", "q"), ld={"p": npp - 1}), outs)]
+        for what, kw, msg in cases:
             rc = call(dev=dev, **kw)
             assert rc == -1, (what, dev, rc)  # NMPC_E_INVALID
             assert L.nmpc_last_error(), what
+            assert L.nmpc_last_error().decode() == msg, (what, dev)
     call(null=("x_bar", "lam_g_bar", "X_bar"))
     assert "seed" in L.nmpc_last_error().decode()
     call(null=("pbar", "q"))

@@ -473,16 +473,24 @@ def test_argument_validation_on_a_live_handle():
         args += [g("dx"), g("dlam_g"), g("dX"), gi, g("delta")]
         return L.nmpc_solve_tangent_batch_dev(*args, vp(0)) if dev else L.nmpc_solve_tangent_batch(*args)
 
+    # each with the full message of its rule; the last four break two rules at once: the earlier
+    # one in the order of the checks answers
+    req, ldm = "required pointer is null (x, p, lam_g, lam_x, lbx, ubx, lbg, ubg, dp)", "leading dimension smaller than the vector length"
+    outs = "dx_out, dlam_g_out and dX_out are all null"
     for dev in (False, True):
-        cases = [("B = 0", dict(B_=0)), ("B < 0", dict(B_=-3)), ("nd = 0", dict(nd_=0)), ("nd < 0", dict(nd_=-1)),
-                 ("every output NULL", dict(null=OUT)), ("ld_x negative", dict(ld={"x": -nw})),
-                 ("ld_dp one direction", dict(ld={"dp": npp}))]
-        cases += [(f"{k} NULL", dict(null=(k,))) for k in names if k != "g"]
-        cases += [(f"ld_{k} short", dict(ld={k: lens[k] - 1})) for k in names]
-        for what, kw in cases:
+        cases = [("B = 0", dict(B_=0), "B <= 0"), ("B < 0", dict(B_=-3), "B <= 0"), ("nd = 0", dict(nd_=0), "nd <= 0"),
+                 ("nd < 0", dict(nd_=-1), "nd <= 0"), ("every output NULL", dict(null=OUT), outs),
+                 ("ld_x negative", dict(ld={"x": -nw}), ldm), ("ld_dp one direction", dict(ld={"dp": npp}), ldm)]
+        cases += [(f"{k} NULL", dict(null=(k,)), req) for k in names if k != "g"]
+        cases += [(f"ld_{k} short", dict(ld={k: lens[k] - 1}), ldm) for k in names]
+        cases += [("B = 0 and nd = 0", dict(B_=0, nd_=0), "B <= 0"), ("nd = 0 and x NULL", dict(nd_=0, null=("x",)), "nd <= 0"),
+                  ("dp NULL and no output", dict(null=("dp",) + tuple(OUT)), req),
+                  ("no output and ld_p short", dict(null=OUT, ld={"p": npp - 1}), outs)]
+        for what, kw, msg in cases:
             rc = call(dev=dev, **kw)
             assert rc == -1, (what, dev, rc)  # NMPC_E_INVALID
             assert L.nmpc_last_error(), what
+            assert L.nmpc_last_error().decode() == msg, (what, dev)
     call(null=OUT)
     assert "dx_out" in L.nmpc_last_error().decode()
     with pytest.raises(_lib.NmpcError):
