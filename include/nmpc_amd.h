@@ -648,6 +648,83 @@ int nmpc_policy_rollout_batch(nmpc_handle* h, int32_t B, int32_t M,
                               double* J_out, double* viol_out, int32_t* nsat_out, double* X_out,
                               double* U_out);
 
+/* The reverse sweep of those rollouts, for a whole batch, in one launch: the gradient of a scalar
+ * loss on the sampled costs and trajectories with respect to everything the rollout reads except
+ * the bounds.  For scenario b with its M samples, seeds Jb_s on J_s, Xb_s on X_s (nx(N+1)) and Ub_s
+ * on the applied controls U_s (nw) define
+ *   L_b = sum_s ( Jb_s J_s + <Xb_s, X_s> + <Ub_s, U_s> )
+ * with J, X and U as nmpc_policy_rollout_batch_dev defines them.  Like the other adjoint entry
+ * points this is a function AT GIVEN TRAJECTORIES: X is the forward call's X_out for the same p,
+ * ubar, Xbar, K, lbx and ubx, and is not recomputed.  Per sample, with x_k = X[s, k], backwards:
+ *   lam_N = Xb_N
+ *   for k = N-1 ... 0:
+ *     u_raw = ubar_k + K_k (x_k - Xbar_k),  u_k = clamp(u_raw)      (the forward's operations)
+ *     mask_r = 1 where u_k[r] == u_raw[r], else 0     (the forward's nsat rule: u_raw exactly on a
+ *                                                      bound counts as unclamped, derivative 1)
+ *     A_k = d x_{k+1} / d x_k,  B_k = d x_{k+1} / d u_k   at (x_k, u_k)
+ *     mu     = mask . (B_k^T lam_{k+1} + Ub_k)
+ *     wbar_k = lam_{k+1}
+ *     lam_k  = Jb grad_x l_k(x_k; p) + Xb_k + A_k^T lam_{k+1} + K_k^T mu
+ *     ubar_bar_k += mu;   K_bar_k += mu (x_k - Xbar_k)^T;   Xbar_bar_k -= K_k^T mu
+ *     p_bar[target x, y] -= Jb (grad_x l_k)[0, 1]   (l depends on position and target through their difference)
+ *     p_bar[w1_pidx] += Jb dd_k,  p_bar[w2_pidx] += Jb (Q_k - 1)    (where the index is set: the
+ *                       target distance and the field-of-view term; the no-gimbal model has no w2 term)
+ *   e0_bar = lam_0;   p_bar[x0 block] += lam_0
+ * e0, w and the row bounds are no inputs: given X the sweep does not depend on them.  viol is a
+ * maximum and is NOT differentiated; a caller who wants a row penalty seeds Xb with its gradient.
+ * The clamp bounds receive no gradient.
+ * Inputs (leading dimension: 0 shares one column, or one set of seeds, with every scenario, else >=
+ * the vector length):
+ *   p    (np x B)          required        ubar (nw x B)          required
+ *   Xbar (nx(N+1) x B)     required        K    (nu nx N x B)     optional (NULL: open loop)
+ *   lbx, ubx (nw x B)      optional, each
+ *   X    (nx(N+1) x M x B) required: the forward call's X_out
+ *   Jb   (M x B)           seed            Xb   (nx(N+1) x M x B) seed, X_out's layout
+ *   Ub   (nw x M x B)      seed, U_out's layout
+ * Each seed may be NULL and then contributes nothing; at least one must be given.
+ * Outputs, each may be NULL, at least one of the six double outputs must be given:
+ *   ubar_bar_out (nw x B), K_bar_out (nu nx N x B, K_out's layout), Xbar_bar_out (nx(N+1) x B, stage
+ *   N exactly 0), p_bar_out (np x B): SUMMED over the scenario's M samples.  An entry of p that J, X
+ *   and U do not read (an obstacle centre, the target's third entry, tail entries) is exactly 0
+ *   e0_bar_out (nx x M x B, e0's layout), w_bar_out (nx N x M x B, w's layout): per sample
+ *   nsat_out (M x B, int32): the clamp count of the recomputed controls; equal to the forward's
+ *   nsat when the sweep saw the clamp pattern the forward saw
+ * K_bar_out and Xbar_bar_out need K (with K NULL nothing depends on them).
+ * The sums over samples are sums in a FIXED order: within a block of 64 samples the order depends
+ * on the sample numbers alone, never on the data, and the blocks are added in ascending order; no
+ * floating-point atomics are used, so two identical calls agree bitwise, and the result at M > 64
+ * is fl(sum over samples 0 ... 63 + sum over samples 64 ... 127 + ...).  Being a sum, a reduced
+ * output takes a NaN from any one sample: a NaN in a sample's X, seeds, controls or the bounds it
+ * meets makes that sample's e0_bar and w_bar NaN and every entry of its own scenario's reduced
+ * outputs that the rollout reads NaN; other scenarios are untouched.
+ * DEVICE pointers, enqueued on `stream`; never synchronises.  With M <= 64 it needs no workspace
+ * and leaves the handle's memory untouched; with M > 64 the per-block partial sums (ceil(M / 64) x
+ * (nw + nu nx N + nx (N+1) + np) doubles per scenario) go to the handle's workspace, grown only when
+ * it does not cover them yet.
+ * A NULL handle, B <= 0, M <= 0 (or M > 64 x 65535), a NULL p, ubar, Xbar or X, Jb, Xb and Ub all
+ * NULL, the six double outputs all NULL, K_bar_out or Xbar_bar_out with a NULL K, or a leading
+ * dimension that is neither 0 nor >= the vector length return NMPC_E_INVALID before any device call. */
+int nmpc_policy_rollout_adjoint_batch_dev(nmpc_handle* h, int32_t B, int32_t M,
+                                          const double* p, int64_t ld_p, const double* ubar, int64_t ld_ubar,
+                                          const double* Xbar, int64_t ld_Xbar, const double* K, int64_t ld_K,
+                                          const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx,
+                                          const double* X, int64_t ld_X, const double* Jb, int64_t ld_Jb,
+                                          const double* Xb, int64_t ld_Xb, const double* Ub, int64_t ld_Ub,
+                                          double* ubar_bar_out, double* K_bar_out, double* Xbar_bar_out,
+                                          double* p_bar_out, double* e0_bar_out, double* w_bar_out,
+                                          int32_t* nsat_out, void* stream);
+
+/* Same with HOST pointers; synchronous (staged through the handle's device buffer). */
+int nmpc_policy_rollout_adjoint_batch(nmpc_handle* h, int32_t B, int32_t M,
+                                      const double* p, int64_t ld_p, const double* ubar, int64_t ld_ubar,
+                                      const double* Xbar, int64_t ld_Xbar, const double* K, int64_t ld_K,
+                                      const double* lbx, int64_t ld_lbx, const double* ubx, int64_t ld_ubx,
+                                      const double* X, int64_t ld_X, const double* Jb, int64_t ld_Jb,
+                                      const double* Xb, int64_t ld_Xb, const double* Ub, int64_t ld_Ub,
+                                      double* ubar_bar_out, double* K_bar_out, double* Xbar_bar_out,
+                                      double* p_bar_out, double* e0_bar_out, double* w_bar_out,
+                                      int32_t* nsat_out);
+
 /* Optional per-iteration trace (debugging / parity): when enabled, the next
  * solve records NMPC_TRACE_FIELDS doubles per iteration per scenario into a
  * device buffer readable with nmpc_read_trace (host pointer,

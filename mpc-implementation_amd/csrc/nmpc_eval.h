@@ -194,7 +194,25 @@ struct RollIO {
   double *X, *U;
 };
 
+// DEVICE pointers, layouts and leading dimensions as nmpc_policy_rollout_adjoint_batch_dev
+// (include/nmpc_amd.h); p, ubar, Xbar and X are required, one of the seeds Jb / Xb / Ub and one of
+// the six double outputs; K_bar and Xbar_bar only with K
+struct RollAdjIO {
+  const double *p, *ubar, *Xbar, *K, *lbx, *ubx, *X, *Jb, *Xb, *Ub;
+  long long ld_p, ld_ubar, ld_Xbar, ld_K, ld_lbx, ld_ubx, ld_X, ld_Jb, ld_Xb, ld_Ub;
+  double *ubar_bar, *K_bar, *Xbar_bar, *p_bar, *e0_bar, *w_bar;
+  int* nsat;
+  double* ws;  // M > 64 only: B x ceil(M / 64) x (nw + nu nx N + nx (N+1) + np) doubles of the handle's workspace
+};
+
 }  // namespace nmpc_impl
+
+// Enqueues the reverse sweep of the policy rollouts of B scenarios x M samples on `stream`:
+// B x ceil(M / 64) wavefronts laid out as nmpc_policy_rollout_launch's and, with more than one
+// block of samples, a second kernel that adds the blocks' partial sums (nred doubles per block) in
+// block order.  Same contract as nmpc_eval_launch.
+int nmpc_policy_rollout_adjoint_launch(const nmpc_impl::Params* dprm, int B, int M, const nmpc_impl::RollAdjIO& io,
+                                       int nred, void* stream);
 
 // Enqueues the policy rollouts of B scenarios x M samples on `stream`: B x ceil(M / 64)
 // wavefronts, sample s of scenario b on lane s % 64 of wavefront (b, s / 64).  Same contract as

@@ -228,3 +228,6 @@ int nmpc_eval_launch(const Params* dprm, int B, const EvalIO& io, void* stream) 
 
 // disturbance rollouts of that policy on the plant, one lane per sample: a ninth kernel of this unit
 #include "nmpc_policy_rollout.hip"
+
+// the reverse sweep of those rollouts, one lane per sample again: a tenth kernel of this unit
+#include "nmpc_policy_rollout_adjoint.hip"

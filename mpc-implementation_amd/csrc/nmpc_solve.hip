@@ -6219,6 +6219,76 @@ int nmpc_policy_rollout_batch(nmpc_handle* h, int32_t B, int32_t M, const double
   return staged(h, B, a, roll_launch, "policy rollout", 0);
 }
 
+// ---- the reverse sweep of those rollouts (kernel: nmpc_policy_rollout_adjoint.hip): inputs p,
+// ubar, Xbar, K, lbx, ubx, X and the seeds Jb, Xb, Ub; outputs ubar_bar, K_bar, Xbar_bar, p_bar,
+// e0_bar, w_bar and the M counts nsat
+static int rolladj_check(const nmpc_handle* h, int32_t B, CallArgs& a) {
+  const char* count = nullptr;
+  if (a.n <= 0) count = "M <= 0";
+  else if (a.n > WAVE * 65535) count = "M > 64 x 65535";  // (no M + 63: it overflows near INT_MAX)
+  const char* own = nullptr;
+  if (all_null(a.in + 7, 3)) own = "every seed pointer is null (Jb, Xb, Ub)";
+  else if (all_null(a.out, 6))
+    own = "ubar_bar_out, K_bar_out, Xbar_bar_out, p_bar_out, e0_bar_out and w_bar_out are all null";
+  else if (!a.in[3] && (a.out[1] || a.out[2])) own = "K_bar_out and Xbar_bar_out need K";
+  return check(h, B, count, a, 0x47, "required pointer is null (p, ubar, Xbar, X)", own,
+               [](const Params& P, CallArgs& a) {
+                 const size_t nw = P.nwE, nx = P.nxE, nu = P.nuE, N = P.N, nX = nx * (N + 1), m = a.n;
+                 set_lens(a.vlen, {(size_t)P.npE, nw, nX, nu * nx * N, nw, nw, nX * m, m, nX * m, nw * m});
+                 set_lens(a.olen, {nw, nu * nx * N, nX, (size_t)P.npE, nx * m, nx * N * m});
+                 a.ilen = m;
+               });
+}
+// doubles of one block's partial sums: ubar_bar, K_bar, Xbar_bar, p_bar
+static int rolladj_nred(const Params& P) { return P.nwE + P.nuE * P.nxE * P.N + P.nxE * (P.N + 1) + P.npE; }
+// workspace per scenario: none while one block of 64 samples holds the scenario's (the sums go
+// straight to the outputs) or no summed output is asked for, else one slice of partial sums per block
+static int rolladj_ws(const nmpc_handle* h, const CallArgs& a) {
+  const int nblk = (a.n + WAVE - 1) / WAVE;
+  return nblk > 1 && !all_null(a.out, 4) ? nblk * rolladj_nred(h->hp) : 0;
+}
+static int rolladj_launch(const nmpc_handle* h, int32_t B, const CallArgs& a, void* stream) {
+  RollAdjIO io;
+  io.p = a.in[0]; io.ubar = a.in[1]; io.Xbar = a.in[2]; io.K = a.in[3]; io.lbx = a.in[4]; io.ubx = a.in[5];
+  io.X = a.in[6]; io.Jb = a.in[7]; io.Xb = a.in[8]; io.Ub = a.in[9];
+  io.ld_p = a.ld[0]; io.ld_ubar = a.ld[1]; io.ld_Xbar = a.ld[2]; io.ld_K = a.ld[3]; io.ld_lbx = a.ld[4];
+  io.ld_ubx = a.ld[5]; io.ld_X = a.ld[6]; io.ld_Jb = a.ld[7]; io.ld_Xb = a.ld[8]; io.ld_Ub = a.ld[9];
+  io.ubar_bar = a.out[0]; io.K_bar = a.out[1]; io.Xbar_bar = a.out[2]; io.p_bar = a.out[3];
+  io.e0_bar = a.out[4]; io.w_bar = a.out[5]; io.nsat = a.iout;
+  io.ws = h->dws;
+  return nmpc_policy_rollout_adjoint_launch(h->dprm, (int)B, (int)a.n, io, rolladj_nred(h->hp), stream);
+}
+
+int nmpc_policy_rollout_adjoint_batch_dev(nmpc_handle* h, int32_t B, int32_t M, const double* p, int64_t ld_p,
+                                          const double* ubar, int64_t ld_ubar, const double* Xbar, int64_t ld_Xbar,
+                                          const double* K, int64_t ld_K, const double* lbx, int64_t ld_lbx,
+                                          const double* ubx, int64_t ld_ubx, const double* X, int64_t ld_X,
+                                          const double* Jb, int64_t ld_Jb, const double* Xb, int64_t ld_Xb,
+                                          const double* Ub, int64_t ld_Ub, double* ubar_bar_out, double* K_bar_out,
+                                          double* Xbar_bar_out, double* p_bar_out, double* e0_bar_out,
+                                          double* w_bar_out, int32_t* nsat_out, void* stream) {
+  CallArgs a{{p, ubar, Xbar, K, lbx, ubx, X, Jb, Xb, Ub},
+             {ld_p, ld_ubar, ld_Xbar, ld_K, ld_lbx, ld_ubx, ld_X, ld_Jb, ld_Xb, ld_Ub}, 10,
+             {ubar_bar_out, K_bar_out, Xbar_bar_out, p_bar_out, e0_bar_out, w_bar_out}, 6, nsat_out, 0, M};
+  if (int rc = rolladj_check(h, B, a)) return rc;
+  return enqueue(h, B, a, stream, rolladj_launch, "policy rollout adjoint", rolladj_ws(h, a));
+}
+
+int nmpc_policy_rollout_adjoint_batch(nmpc_handle* h, int32_t B, int32_t M, const double* p, int64_t ld_p,
+                                      const double* ubar, int64_t ld_ubar, const double* Xbar, int64_t ld_Xbar,
+                                      const double* K, int64_t ld_K, const double* lbx, int64_t ld_lbx,
+                                      const double* ubx, int64_t ld_ubx, const double* X, int64_t ld_X,
+                                      const double* Jb, int64_t ld_Jb, const double* Xb, int64_t ld_Xb,
+                                      const double* Ub, int64_t ld_Ub, double* ubar_bar_out, double* K_bar_out,
+                                      double* Xbar_bar_out, double* p_bar_out, double* e0_bar_out, double* w_bar_out,
+                                      int32_t* nsat_out) {
+  CallArgs a{{p, ubar, Xbar, K, lbx, ubx, X, Jb, Xb, Ub},
+             {ld_p, ld_ubar, ld_Xbar, ld_K, ld_lbx, ld_ubx, ld_X, ld_Jb, ld_Xb, ld_Ub}, 10,
+             {ubar_bar_out, K_bar_out, Xbar_bar_out, p_bar_out, e0_bar_out, w_bar_out}, 6, nsat_out, 0, M};
+  if (int rc = rolladj_check(h, B, a)) return rc;
+  return staged(h, B, a, rolladj_launch, "policy rollout adjoint", rolladj_ws(h, a));
+}
+
 int nmpc_shift_dev(nmpc_handle* h, int32_t B, double* p, int64_t ld_p, const double* u_sol, double* w_out,
                    const double* v_t, const double* w_t, void* stream) {
   if (!h) return fail(NMPC_E_INVALID, "null handle");

@@ -34,6 +34,7 @@ EXPORTS = (
     "nmpc_solve_tangent_batch", "nmpc_solve_tangent_batch_dev",
     "nmpc_solve_policy_batch", "nmpc_solve_policy_batch_dev",
     "nmpc_policy_rollout_batch", "nmpc_policy_rollout_batch_dev",
+    "nmpc_policy_rollout_adjoint_batch", "nmpc_policy_rollout_adjoint_batch_dev",
 )
 
 _OPT_INT = ("max_iter", "acceptable_iter", "max_soc", "max_soft_resto_iters",
@@ -138,6 +139,10 @@ def lib():
     if hasattr(L, "nmpc_policy_rollout_batch") or not os.environ.get("NMPC_LIB"):
         L.nmpc_policy_rollout_batch.argtypes = ([vp, C.c_int32, C.c_int32] + [dp, i64] * 10 + [dp, dp, i32p, dp, dp])
         L.nmpc_policy_rollout_batch_dev.argtypes = [vp, C.c_int32, C.c_int32] + [vp, i64] * 10 + [vp] * 5 + [vp]
+    if hasattr(L, "nmpc_policy_rollout_adjoint_batch") or not os.environ.get("NMPC_LIB"):
+        L.nmpc_policy_rollout_adjoint_batch.argtypes = ([vp, C.c_int32, C.c_int32] + [dp, i64] * 10 + [dp] * 6 + [i32p])
+        L.nmpc_policy_rollout_adjoint_batch_dev.argtypes = ([vp, C.c_int32, C.c_int32] + [vp, i64] * 10 + [vp] * 7
+                                                            + [vp])
     L.nmpc_set_trace.argtypes = [vp, C.c_int32]
     L.nmpc_read_trace.argtypes = [vp, C.c_int32, dp]
     L.nmpc_shift_dev.argtypes = [vp, C.c_int32, vp, i64, vp, vp, vp, vp, vp]

@@ -102,6 +102,68 @@ def _function():
     return _Solve
 
 
+@functools.lru_cache(maxsize=None)
+def _rollout_function():
+    import torch
+
+    class _Rollout(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, solver, p, ubar, Xbar, K, e0, w, lbx, ubx):
+            det = [None if t is None else t.detach().contiguous() for t in (p, ubar, Xbar, K, e0, w, lbx, ubx)]
+            pd, ud, Xd, Kd, ed, wd, lo, hi = det
+            _, nu, nx = solver._policy_dims()
+            ctx.k_view = Kd is not None and tuple(Kd.shape[-2:]) == (nu, nx)
+            if ctx.k_view:  # policy_device's view (…, nu, nx): to the kernel's column-major blocks
+                Kd = Kd.transpose(-1, -2).contiguous()
+            r = solver.policy_rollout_device(pd, ud, Xd, Kd, ed, w=wd, lbx=lo, ubx=hi, want=("J", "X", "U"))
+            ctx.set_materialize_grads(False)  # an output the loss does not read seeds nothing
+            ctx.solver, ctx.ins, ctx.X = solver, (pd, ud, Xd, Kd, lo, hi), r["X"]
+            ctx.has_w = wd is not None
+            return r["J"], r["X"], r["U"]
+
+        @staticmethod
+        def backward(ctx, Jb, Xb, Ub):
+            s = ctx.solver
+            pd, ud, Xd, Kd, lo, hi = ctx.ins
+            if Jb is None and Xb is None and Ub is None:
+                return (None,) * 9
+            need = ctx.needs_input_grad  # (solver, p, ubar, Xbar, K, e0, w, lbx, ubx)
+            names = ((1, "p_bar"), (2, "ubar_bar"), (3, "Xbar_bar"), (4, "K_bar"), (5, "e0_bar"), (6, "w_bar"))
+            want = tuple(n for i, n in names if need[i] and not (Kd is None and n in ("K_bar", "Xbar_bar"))
+                         and not (n == "w_bar" and not ctx.has_w))
+            if not want:
+                return (None,) * 9
+            seeds = [None if t is None else t.detach().to(torch.float64).contiguous() for t in (Jb, Xb, Ub)]
+            o = s.policy_rollout_adjoint_device(pd, ud, Xd, Kd, ctx.X, *seeds, lbx=lo, ubx=hi, want=want)
+            B = ctx.X.shape[0]
+
+            def grad(i, n, like):  # a shared input's gradient is the sum over the scenarios
+                g = o.get(n)
+                if g is None:
+                    return None
+                if n == "K_bar" and ctx.k_view:
+                    g = g.transpose(-1, -2)
+                return g.sum(0) if like.dim() == g.dim() - 1 and g.shape[0] == B else g
+
+            return (None, grad(1, "p_bar", pd), grad(2, "ubar_bar", ud), grad(3, "Xbar_bar", Xd),
+                    None if Kd is None else grad(4, "K_bar", Kd), o.get("e0_bar"), o.get("w_bar"), None, None)
+
+    return _Rollout
+
+
+def policy_rollout(solver, p, ubar, Xbar, K, e0, w=None, lbx=None, ubx=None):
+    """M disturbance rollouts per scenario of the clamped policy (:meth:`Solver.policy_rollout_device`,
+    whose shapes the arguments have; CUDA float64 tensors, ``e0`` (B,M,nx) and ``w`` (B,M,N,nx) with
+    the B) as a differentiable function: returns ``J`` (B,M), ``X`` (B,M,N+1,nx) and the applied
+    controls ``U`` (B,M,N,nu), through which ``backward`` reaches ``p``, ``ubar``, ``Xbar``, ``K``,
+    ``e0`` and ``w`` -- each only if it requires grad -- by one
+    :meth:`Solver.policy_rollout_adjoint_device` launch.  The clamp bounds ``lbx`` / ``ubx`` get no
+    gradient, and ``viol``, a maximum, is not an output.  A control the clamp changed passes no
+    gradient (u_raw exactly on a bound counts as unclamped).  Neither pass copies to the host or
+    synchronises."""
+    return _rollout_function().apply(solver, p, ubar, Xbar, K, e0, w, lbx, ubx)
+
+
 def solve(solver, p, lbx, ubx, lbg, ubg, x0=None, backward="host"):
     """Solves the batch at the parameters ``p`` -- a (B, np) float64 CUDA tensor that may require
     grad -- and returns the solution ``x`` (B, nw) and its state trajectory ``X`` (B, nx(N+1)) as

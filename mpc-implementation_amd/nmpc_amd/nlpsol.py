@@ -1096,6 +1096,119 @@ class Solver:
         _lib.check(_lib.lib().nmpc_policy_rollout_batch(self._h, B, M, *_flat_ins(arrs), *ptr))
         return res
 
+    # ---- the reverse sweep of those rollouts (nmpc_policy_rollout_adjoint_batch)
+    ROLLOUT_ADJ_OUT = ("ubar_bar", "K_bar", "Xbar_bar", "p_bar", "e0_bar", "w_bar", "nsat")
+
+    def _rollout_adjoint_shapes(self, B, M):
+        N, nu, nx = self._policy_dims()
+        return {"ubar_bar": (B, self.nw), "K_bar": (B, N, nx, nu), "Xbar_bar": (B, N + 1, nx), "p_bar": (B, self.np),
+                "e0_bar": (B, M, nx), "w_bar": (B, M, N, nx), "nsat": (B, M)}
+
+    def policy_rollout_adjoint_device(self, p, ubar, Xbar, K, X, Jb=None, Xb=None, Ub=None, lbx=None, ubx=None,
+                                      out: dict | None = None, want=("ubar_bar", "p_bar"), stream=None):
+        """The reverse sweep of :meth:`policy_rollout_device` at its trajectories ``X`` (B,M,N+1,nx)
+        (``nmpc_policy_rollout_adjoint_batch_dev``, whose comment states the recursion): the gradient
+        of sum_s (Jb_s J_s + <Xb_s, X_s> + <Ub_s, U_s>) per scenario, torch CUDA float64 tensors in
+        and out.  ``p``, ``ubar``, ``Xbar``, ``K``, ``lbx`` and ``ubx`` are the forward call's; the
+        seeds ``Jb`` (B,M), ``Xb`` (B,M,N+1,nx) and ``Ub`` (B,M,N,nu) may each be None or shared
+        (without the B), one at least is required.  Returns a dict with the outputs named in
+        ``want`` and those preallocated in ``out``: ``ubar_bar`` (B,nw), ``K_bar`` (B,N,nx,nu) -- the
+        kernel's column-major blocks, the layout of :meth:`policy_device`'s raw ``K`` --,
+        ``Xbar_bar`` (B,N+1,nx) and ``p_bar`` (B,np), summed over the M samples; ``e0_bar`` (B,M,nx)
+        and ``w_bar`` (B,M,N,nx) per sample; ``nsat`` (B,M) int32, recounted.  ``K_bar`` and
+        ``Xbar_bar`` need ``K``.  Enqueued on ``stream`` (default = current); never synchronises the
+        host and reads nothing back; uses the handle's workspace only when M > 64."""
+        import torch  # plumbing only: device memory and streams
+
+        N, nu, nx = self._policy_dims()
+        assert X.dim() in (3, 4) and tuple(X.shape[-2:]) == (N + 1, nx), ("X", tuple(X.shape))
+        M = X.shape[-3]
+        B = None
+        for t, lead in ((X, 4), (p, 2), (ubar, 2), (Xbar, 3), (Jb, 2), (Xb, 4), (Ub, 4)):
+            if t is not None and t.dim() == lead:
+                B = t.shape[0]
+                break
+        if B is None:
+            raise ValueError("policy_rollout_adjoint_device: no argument carries the batch size")
+        if K is not None and tuple(K.shape[-2:]) == (nu, nx):
+            K = K.transpose(-1, -2)  # policy_device's view back to the kernel's column-major blocks
+        if p is None or ubar is None or Xbar is None:
+            raise ValueError("p, ubar and Xbar are required")
+        if Jb is None and Xb is None and Ub is None:
+            raise ValueError("policy_rollout_adjoint_device: one of the seeds Jb, Xb, Ub is required")
+        ins = _dev_ins((("p", p, (self.np,)), ("ubar", ubar, (self.nw,)), ("Xbar", Xbar, (N + 1, nx)),
+                        ("K", K, (N, nx, nu)), ("lbx", lbx, (self.nw,)), ("ubx", ubx, (self.nw,)),
+                        ("X", X, (M, N + 1, nx)), ("Jb", Jb, (M,)), ("Xb", Xb, (M, N + 1, nx)),
+                        ("Ub", Ub, (M, N, nu))), B)
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        shapes = self._rollout_adjoint_shapes(B, M)
+        res = dict(out or {})
+        with torch.cuda.stream(stream):
+            for k in want:
+                if res.get(k) is None:
+                    res[k] = torch.empty(shapes[k], dtype=torch.int32 if k == "nsat" else torch.float64,
+                                         device=X.device)
+        if all(res.get(k) is None for k in self.ROLLOUT_ADJ_OUT[:6]):
+            raise ValueError("policy_rollout_adjoint_device: one of " + ", ".join(self.ROLLOUT_ADJ_OUT[:6])
+                             + " is required")
+        if K is None and (res.get("K_bar") is not None or res.get("Xbar_bar") is not None):
+            raise ValueError("policy_rollout_adjoint_device: K_bar and Xbar_bar need K")
+        ptr = _dev_outs(res, [(k, shapes[k]) for k in self.ROLLOUT_ADJ_OUT])
+        _lib.check(_lib.lib().nmpc_policy_rollout_adjoint_batch_dev(self._h, B, M, *ins, *ptr, _stream_ptr(stream)))
+        return {k: v for k, v in res.items() if v is not None}
+
+    def policy_rollout_adjoint(self, p, ubar, Xbar, K, X, Jb=None, Xb=None, Ub=None, lbx=None, ubx=None,
+                               want=("ubar_bar", "K_bar", "Xbar_bar", "p_bar", "e0_bar", "w_bar", "nsat")):
+        """:meth:`policy_rollout_adjoint_device` through the host entry point
+        (``nmpc_policy_rollout_adjoint_batch``), NumPy arrays in the same scenario-major shapes;
+        ``K`` (B,N,nu,nx) in row-major blocks, as :meth:`policy_fused` returns them, or None, and
+        ``K_bar`` (B,N,nu,nx) likewise.  Each input may be shared (without the B).  Returns
+        the outputs named in ``want`` (``K_bar`` and ``Xbar_bar`` are left out when K is None)."""
+        N, nu, nx = self._policy_dims()
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim not in (3, 4) or X.shape[-2:] != (N + 1, nx):
+            raise ValueError(f"X: expected (M,{N + 1},{nx}) or (B,M,{N + 1},{nx}), got shape {X.shape}")
+        M = X.shape[-3]
+        if K is not None:
+            K = np.asarray(K, dtype=np.float64)
+            if K.shape[-2:] != (nu, nx):
+                raise ValueError(f"K: expected blocks of ({nu},{nx}), got shape {K.shape}")
+            K = np.swapaxes(K, -1, -2)  # to the kernel's column-major blocks
+        fields = (("p", p, (self.np,)), ("ubar", ubar, (self.nw,)), ("Xbar", Xbar, (N + 1, nx)), ("K", K, (N, nx, nu)),
+                  ("lbx", lbx, (self.nw,)), ("ubx", ubx, (self.nw,)), ("X", X, (M, N + 1, nx)), ("Jb", Jb, (M,)),
+                  ("Xb", Xb, (M, N + 1, nx)), ("Ub", Ub, (M, N, nu)))
+        arrs, B = [], None
+        for name, a, tail in fields:
+            if a is None:
+                if name in ("p", "ubar", "Xbar"):
+                    raise ValueError(f"{name} is required")
+                arrs.append((None, 0))
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape == tail:
+                arrs.append((a, 0))
+                continue
+            if a.shape[1:] != tail or B not in (None, a.shape[0]):
+                raise ValueError(f"{name}: expected {tail} or (B,) + {tail}, got shape {a.shape}")
+            B = a.shape[0]
+            arrs.append((a, int(np.prod(tail))))
+        if B is None:
+            raise ValueError("policy_rollout_adjoint: no argument carries the batch size")
+        if Jb is None and Xb is None and Ub is None:
+            raise ValueError("policy_rollout_adjoint: one of the seeds Jb, Xb, Ub is required")
+        shapes = self._rollout_adjoint_shapes(B, M)
+        res = {k: np.empty(shapes[k], dtype=np.int32 if k == "nsat" else np.float64) for k in self.ROLLOUT_ADJ_OUT
+               if k in want and not (K is None and k in ("K_bar", "Xbar_bar"))}
+        if not any(k in res for k in self.ROLLOUT_ADJ_OUT[:6]):
+            raise ValueError("policy_rollout_adjoint: one of " + ", ".join(self.ROLLOUT_ADJ_OUT[:6]) + " is required")
+        ptr = [None if k not in res else (res[k].ctypes.data_as(_IP) if k == "nsat" else _dptr(res[k]))
+               for k in self.ROLLOUT_ADJ_OUT]
+        _lib.check(_lib.lib().nmpc_policy_rollout_adjoint_batch(self._h, B, M, *_flat_ins(arrs), *ptr))
+        if "K_bar" in res:
+            res["K_bar"] = np.ascontiguousarray(np.swapaxes(res["K_bar"], -1, -2))
+        return res
+
     def shift_device(self, p, u_sol, w_out, v_t, w_t, stream=None):
         """Closed-loop shift on device (Python/NMPC_TT.py:13-30), see nmpc_shift_dev."""
         import torch

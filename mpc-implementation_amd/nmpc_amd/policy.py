@@ -71,3 +71,38 @@ def rollout(solver, pol: dict, sol: dict, p, e0, w=None, c=None, lbx=None, ubx=N
     raw = pol["raw"]
     return solver.policy_rollout_device(p, ubar.contiguous(), raw["X"], raw["K"] if feedback else None, e0, w=w,
                                         lbx=lbx, ubx=ubx, lbg=lbg, ubg=ubg, out=out, want=want, stream=stream)
+
+
+def rollout_grad(solver, pol: dict, sol: dict, p, X, Jb=None, Xb=None, Ub=None, c=None, lbx=None, ubx=None,
+                 feedback: bool = True, out: dict | None = None, want=("ubar_bar", "p_bar"), stream=None):
+    """The gradient of a loss on :func:`rollout`'s samples, in one launch
+    (``Solver.policy_rollout_adjoint_device``): with ``X`` (B, M, N+1, nx) the trajectories that
+    :func:`rollout` returned for the same ``pol``, ``sol``, ``p``, ``c``, bounds and ``feedback``,
+    and seeds ``Jb`` (B, M) on J, ``Xb`` (B, M, N+1, nx) on X and ``Ub`` (B, M, N, nu) on the applied
+    controls (each may be None, one at least is given), the derivative of
+    sum_s (Jb_s J_s + <Xb_s, X_s> + <Ub_s, U_s>) per scenario with respect to the nominal controls
+    (``ubar_bar`` (B, nw)), the gains (``K_bar`` (B, N, nx, nu), the raw column-major blocks), the
+    plan's states (``Xbar_bar``), the parameters (``p_bar``) and each sample's disturbances
+    (``e0_bar``, ``w_bar``), as asked for in ``want`` or preallocated in ``out``.  With ``c`` given,
+    ubar = u* + sum_d kff^(d) c_d, and the dict also holds ``c_bar`` (B, nd) = <kff^(d), ubar_bar>
+    (``ubar_bar`` is then formed whether asked for or not).  Jb = 1 / M gives the gradient of the
+    mean sampled cost.  Nothing is copied to the host and nothing synchronises."""
+    import torch
+
+    ubar = sol["x"]
+    kff = None
+    if c is not None:
+        kff = pol["kff"]
+        if kff is None:
+            raise ValueError("the policy holds no feedforward: it was formed without directions")
+        cc = c if c.dim() == 2 else c.unsqueeze(0).expand(kff.shape[0], -1)
+        ubar = ubar + torch.einsum("bdn,bd->bn", kff.reshape(kff.shape[0], kff.shape[1], -1), cc)
+        if "ubar_bar" not in want:
+            want = tuple(want) + ("ubar_bar",)
+    raw = pol["raw"]
+    res = solver.policy_rollout_adjoint_device(p, ubar.contiguous(), raw["X"], raw["K"] if feedback else None, X,
+                                               Jb=Jb, Xb=Xb, Ub=Ub, lbx=lbx, ubx=ubx, out=out, want=want,
+                                               stream=stream)
+    if kff is not None:
+        res["c_bar"] = torch.einsum("bdn,bn->bd", kff.reshape(kff.shape[0], kff.shape[1], -1), res["ubar_bar"])
+    return res
