@@ -725,6 +725,64 @@ int nmpc_policy_rollout_adjoint_batch(nmpc_handle* h, int32_t B, int32_t M,
                                       double* p_bar_out, double* e0_bar_out, double* w_bar_out,
                                       int32_t* nsat_out);
 
+/* The closed-loop covariance of that policy around the plan, for a whole batch, in one launch: the
+ * number the rollouts only estimate, and from it the standard deviation of every row and every
+ * control -- what a stochastic-NMPC user tightens lbg / ubg / lbx / ubx by before the next solve
+ * (the "back-offs").  For each of B scenarios and each of nc >= 1 covariance cases c, in fp64 and in
+ * the model's own dimensions (the no-gimbal model: nu = 3, nx = 5), to first order around the plan:
+ *   Sigma_0 = S0[c]
+ *   for k = 0 ... N-1:
+ *     A_k, B_k   = d x_{k+1} / d x_k, d x_{k+1} / d u_k of x_{k+1} = x_k + T f(x_k, u_k) at
+ *                  (Xbar_k, ubar_k): A_out, B_out of nmpc_solve_policy_batch_dev
+ *     Acl_k      = A_k + B_k K_k                        (K NULL: Acl_k = A_k, open loop)
+ *     var_u[k,r] = (K_k Sigma_k K_k^T)[r,r]             (K NULL: 0)
+ *     var_g[k,i] = Sigma_k[bi,bi]                       box row i on state bi
+ *                = g^T Sigma_k[0:2,0:2] g + obs_var[o]  obstacle row o, g = -(x - ox, y - oy) / d at
+ *                                                       Xbar_k, the centre taken from p where the
+ *                                                       descriptor says so
+ *     Sigma_{k+1} = Acl_k Sigma_k Acl_k^T + W[c]        (W NULL: no process noise)
+ *   var_g[N, .] at Sigma_N, Xbar_N
+ *   sigma = sqrt(max(var, 0)); a NaN variance gives NaN (the maximum does not drop it)
+ * The kernel knows nothing about clamps: a control held on its bound passes no feedback, and a
+ * caller who wants that zeroes the control's row of K_k.  W is the same at every stage.
+ * p, ubar, Xbar and K are nmpc_policy_rollout_batch_dev's, so K_out and X_out of
+ * nmpc_solve_policy_batch_dev and the solve's x_out can be passed straight in.
+ * Inputs (leading dimension: 0 shares one column across scenarios, else >= the vector length):
+ *   p       (np x B)         required: read only for obstacle centres taken from p
+ *   ubar    (nw x B)         required        Xbar (nx(N+1) x B)   required
+ *   K       (nu nx N x B)    optional, K_out's layout
+ *   S0      (nx nx nc x B)   required: case c occupies [c nx nx, (c+1) nx nx), column-major
+ *   W       (nx nx nc x B)   optional, as S0
+ *   obs_var (n_obs x B)      optional: the isotropic variance of each obstacle's centre, shared by
+ *                            the cases
+ * Only the lower triangle (i >= j) of each S0 and W block is read; the upper one is taken as its mirror.
+ * Outputs, each may be NULL, at least one must be given; case c of scenario b starts at (b nc + c) n:
+ *   Sigma_out   (nx nx (N+1) x nc x B): block k is Sigma_k, column-major, exactly symmetric
+ *   sigma_u_out (nw x nc x B)         : x_out's layout
+ *   sigma_g_out (ng x nc x B)         : g_out's row order; stage 0's rows are taken at Sigma_0
+ * Cases are independent: a NaN in one case's S0 or W stays in that case.  A NaN K or Xbar (a policy
+ * with info != 0) makes that scenario's Sigma_k (k >= 1) and sigma_u NaN beside untouched
+ * neighbours.  S0 = 0 with W NULL gives exactly 0 everywhere.
+ * DEVICE pointers, enqueued on `stream`; never synchronises, allocates nothing and needs no
+ * workspace (each case's matrices live in on-chip memory): the handle's memory is untouched.
+ * A NULL handle, B <= 0, nc <= 0 (or nc > 65535), a NULL p, ubar, Xbar or S0, Sigma_out, sigma_u_out
+ * and sigma_g_out all NULL, obs_var on a problem with n_obs = 0, or a leading dimension that is
+ * neither 0 nor >= the vector length return NMPC_E_INVALID before any device call. */
+int nmpc_policy_covariance_batch_dev(nmpc_handle* h, int32_t B, int32_t nc,
+                                     const double* p, int64_t ld_p, const double* ubar, int64_t ld_ubar,
+                                     const double* Xbar, int64_t ld_Xbar, const double* K, int64_t ld_K,
+                                     const double* S0, int64_t ld_S0, const double* W, int64_t ld_W,
+                                     const double* obs_var, int64_t ld_obs_var,
+                                     double* Sigma_out, double* sigma_u_out, double* sigma_g_out, void* stream);
+
+/* Same with HOST pointers; synchronous (staged through the handle's device buffer). */
+int nmpc_policy_covariance_batch(nmpc_handle* h, int32_t B, int32_t nc,
+                                 const double* p, int64_t ld_p, const double* ubar, int64_t ld_ubar,
+                                 const double* Xbar, int64_t ld_Xbar, const double* K, int64_t ld_K,
+                                 const double* S0, int64_t ld_S0, const double* W, int64_t ld_W,
+                                 const double* obs_var, int64_t ld_obs_var,
+                                 double* Sigma_out, double* sigma_u_out, double* sigma_g_out);
+
 /* Optional per-iteration trace (debugging / parity): when enabled, the next
  * solve records NMPC_TRACE_FIELDS doubles per iteration per scenario into a
  * device buffer readable with nmpc_read_trace (host pointer,

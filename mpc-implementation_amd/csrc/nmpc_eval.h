@@ -205,7 +205,21 @@ struct RollAdjIO {
   double* ws;  // M > 64 only: B x ceil(M / 64) x (nw + nu nx N + nx (N+1) + np) doubles of the handle's workspace
 };
 
+// DEVICE pointers, layouts and leading dimensions as nmpc_policy_covariance_batch_dev
+// (include/nmpc_amd.h); p, ubar, Xbar and S0 are required, and one of Sigma / sigma_u / sigma_g.
+// No workspace: each case's matrices live in LDS
+struct CovIO {
+  const double *p, *ubar, *Xbar, *K, *S0, *W, *obs_var;
+  long long ld_p, ld_ubar, ld_Xbar, ld_K, ld_S0, ld_W, ld_obs_var;
+  double *Sigma, *sigma_u, *sigma_g;
+};
+
 }  // namespace nmpc_impl
+
+// Enqueues the closed-loop covariances of B scenarios x nc cases on `stream`: B x nc wavefronts,
+// one per (scenario, case), lane = entry of the 8 x 8 matrix.  Same contract as nmpc_eval_launch.
+int nmpc_policy_covariance_launch(const nmpc_impl::Params* dprm, int B, int nc, const nmpc_impl::CovIO& io,
+                                  void* stream);
 
 // Enqueues the reverse sweep of the policy rollouts of B scenarios x M samples on `stream`:
 // B x ceil(M / 64) wavefronts laid out as nmpc_policy_rollout_launch's and, with more than one

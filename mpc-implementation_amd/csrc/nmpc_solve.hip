@@ -5643,7 +5643,7 @@ int nmpc_solve_batch(nmpc_handle* h, int32_t B, const double* x0, int64_t ld_x0,
 }
 
 // ---- the batched entry points at given points.  One argument block, one check, one enqueue and
-// one staging routine serve the nine entry-point pairs (X_batch on host pointers, X_batch_dev on
+// one staging routine serve the eleven entry-point pairs (X_batch on host pointers, X_batch_dev on
 // device pointers); a pair adds its own rules, its table of lengths and its launch callback
 struct CallArgs {
   // the inputs in the C argument order (absent ones null) and their leading dimensions
@@ -6287,6 +6287,56 @@ int nmpc_policy_rollout_adjoint_batch(nmpc_handle* h, int32_t B, int32_t M, cons
              {ubar_bar_out, K_bar_out, Xbar_bar_out, p_bar_out, e0_bar_out, w_bar_out}, 6, nsat_out, 0, M};
   if (int rc = rolladj_check(h, B, a)) return rc;
   return staged(h, B, a, rolladj_launch, "policy rollout adjoint", rolladj_ws(h, a));
+}
+
+// ---- the closed-loop covariance of the policy and its rows' standard deviations (kernel:
+// nmpc_policy_covariance.hip): inputs p, ubar, Xbar, K, S0, W, obs_var; outputs Sigma, sigma_u,
+// sigma_g of the nc cases
+static int cov_check(const nmpc_handle* h, int32_t B, CallArgs& a) {
+  const char* count = nullptr;
+  if (a.n <= 0) count = "nc <= 0";
+  else if (a.n > 65535) count = "nc > 65535";
+  const char* own = nullptr;
+  if (all_null(a.out, 3)) own = "Sigma_out, sigma_u_out and sigma_g_out are all null";
+  else if (h && a.in[6] && h->hp.nobs == 0) own = "obs_var given for a problem without obstacles";
+  return check(h, B, count, a, 0x17, "required pointer is null (p, ubar, Xbar, S0)", own,
+               [](const Params& P, CallArgs& a) {
+                 const size_t nw = P.nwE, nx = P.nxE, nu = P.nuE, N = P.N, nc = a.n;
+                 set_lens(a.vlen, {(size_t)P.npE, nw, nx * (N + 1), nu * nx * N, nx * nx * nc, nx * nx * nc,
+                                   (size_t)P.nobs});
+                 set_lens(a.olen, {nx * nx * (N + 1) * nc, nw * nc, (size_t)P.ng * nc});
+               });
+}
+static int cov_launch(const nmpc_handle* h, int32_t B, const CallArgs& a, void* stream) {
+  CovIO io;
+  io.p = a.in[0]; io.ubar = a.in[1]; io.Xbar = a.in[2]; io.K = a.in[3]; io.S0 = a.in[4]; io.W = a.in[5];
+  io.obs_var = a.in[6];
+  io.ld_p = a.ld[0]; io.ld_ubar = a.ld[1]; io.ld_Xbar = a.ld[2]; io.ld_K = a.ld[3]; io.ld_S0 = a.ld[4];
+  io.ld_W = a.ld[5]; io.ld_obs_var = a.ld[6];
+  io.Sigma = a.out[0]; io.sigma_u = a.out[1]; io.sigma_g = a.out[2];
+  return nmpc_policy_covariance_launch(h->dprm, (int)B, (int)a.n, io, stream);
+}
+
+int nmpc_policy_covariance_batch_dev(nmpc_handle* h, int32_t B, int32_t nc, const double* p, int64_t ld_p,
+                                     const double* ubar, int64_t ld_ubar, const double* Xbar, int64_t ld_Xbar,
+                                     const double* K, int64_t ld_K, const double* S0, int64_t ld_S0,
+                                     const double* W, int64_t ld_W, const double* obs_var, int64_t ld_obs_var,
+                                     double* Sigma_out, double* sigma_u_out, double* sigma_g_out, void* stream) {
+  CallArgs a{{p, ubar, Xbar, K, S0, W, obs_var}, {ld_p, ld_ubar, ld_Xbar, ld_K, ld_S0, ld_W, ld_obs_var}, 7,
+             {Sigma_out, sigma_u_out, sigma_g_out}, 3, nullptr, 0, nc};
+  if (int rc = cov_check(h, B, a)) return rc;
+  return enqueue(h, B, a, stream, cov_launch, "policy covariance", 0);
+}
+
+int nmpc_policy_covariance_batch(nmpc_handle* h, int32_t B, int32_t nc, const double* p, int64_t ld_p,
+                                 const double* ubar, int64_t ld_ubar, const double* Xbar, int64_t ld_Xbar,
+                                 const double* K, int64_t ld_K, const double* S0, int64_t ld_S0, const double* W,
+                                 int64_t ld_W, const double* obs_var, int64_t ld_obs_var, double* Sigma_out,
+                                 double* sigma_u_out, double* sigma_g_out) {
+  CallArgs a{{p, ubar, Xbar, K, S0, W, obs_var}, {ld_p, ld_ubar, ld_Xbar, ld_K, ld_S0, ld_W, ld_obs_var}, 7,
+             {Sigma_out, sigma_u_out, sigma_g_out}, 3, nullptr, 0, nc};
+  if (int rc = cov_check(h, B, a)) return rc;
+  return staged(h, B, a, cov_launch, "policy covariance", 0);
 }
 
 int nmpc_shift_dev(nmpc_handle* h, int32_t B, double* p, int64_t ld_p, const double* u_sol, double* w_out,

@@ -1209,6 +1209,109 @@ class Solver:
             res["K_bar"] = np.ascontiguousarray(np.swapaxes(res["K_bar"], -1, -2))
         return res
 
+    # ---- the policy's closed-loop covariance and the rows' standard deviations
+    # (nmpc_policy_covariance_batch)
+    COVARIANCE_OUT = ("Sigma", "sigma_u", "sigma_g")
+
+    def _covariance_shapes(self, B, nc):
+        N, nu, nx = self._policy_dims()
+        return {"Sigma": (B, nc, N + 1, nx, nx), "sigma_u": (B, nc, N, nu), "sigma_g": (B, nc, N + 1, self.ng // (N + 1))}
+
+    def policy_covariance_device(self, p, ubar, Xbar, K, S0, W=None, obs_var=None, out: dict | None = None,
+                                 want=("sigma_g", "sigma_u"), stream=None):
+        """The state covariance around the plan under the policy u_k = ubar_k + K_k (x_k - Xbar_k),
+        Sigma_{k+1} = (A_k + B_k K_k) Sigma_k (A_k + B_k K_k)^T + W from Sigma_0 = S0, and the standard
+        deviations of every control and every row (``nmpc_policy_covariance_batch_dev``, whose comment
+        states the recursion), torch CUDA float64 tensors in and out.  ``p``, ``ubar``, ``Xbar`` and ``K``
+        as :meth:`policy_rollout_device` takes them (``K`` None: open loop).  ``S0`` is (B,nc,nx,nx)
+        or shared (nc,nx,nx), one initial covariance per case, and ``W`` likewise or None, the process
+        noise added at every stage; the blocks are column-major, entry (i, j) at ``[..., j, i]``, and
+        only the entries with i >= j are read (a symmetric matrix is passed as it is).  ``obs_var``
+        (B,n_obs) or (n_obs,) or None is the isotropic variance of each obstacle's centre.  Returns a
+        dict with the outputs named in ``want`` and those preallocated in ``out``: ``Sigma``
+        (B,nc,N+1,nx,nx), exactly symmetric; ``sigma_u`` (B,nc,N,nu); ``sigma_g`` (B,nc,N+1,m), stage 0's
+        rows at S0.  The kernel knows nothing about clamps: zero a control's row of K where it is held on
+        its bound.  Enqueued on ``stream`` (default = current); never synchronises the host, reads
+        nothing back and uses no workspace of the handle."""
+        import torch  # plumbing only: device memory and streams
+
+        N, nu, nx = self._policy_dims()
+        if p is None or ubar is None or Xbar is None or S0 is None:
+            raise ValueError("p, ubar, Xbar and S0 are required")
+        assert S0.dim() in (3, 4) and tuple(S0.shape[-2:]) == (nx, nx), ("S0", tuple(S0.shape))
+        nc = S0.shape[-3]
+        B = None
+        for t, lead in ((S0, 4), (p, 2), (ubar, 2), (Xbar, 3), (W, 4), (obs_var, 2)):
+            if t is not None and t.dim() == lead:
+                B = t.shape[0]
+                break
+        if B is None:
+            raise ValueError("policy_covariance_device: no argument carries the batch size")
+        if K is not None and tuple(K.shape[-2:]) == (nu, nx):
+            K = K.transpose(-1, -2)  # policy_device's view back to the kernel's column-major blocks
+        ins = _dev_ins((("p", p, (self.np,)), ("ubar", ubar, (self.nw,)), ("Xbar", Xbar, (N + 1, nx)),
+                        ("K", K, (N, nx, nu)), ("S0", S0, (nc, nx, nx)), ("W", W, (nc, nx, nx)),
+                        ("obs_var", obs_var, (self.spec.n_obs,))), B)
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        shapes = self._covariance_shapes(B, nc)
+        res = dict(out or {})
+        with torch.cuda.stream(stream):
+            for k in want:
+                if res.get(k) is None:
+                    res[k] = torch.empty(shapes[k], dtype=torch.float64, device=S0.device)
+        if all(res.get(k) is None for k in self.COVARIANCE_OUT):
+            raise ValueError("policy_covariance_device: one of Sigma, sigma_u, sigma_g is required")
+        ptr = _dev_outs(res, shapes.items())
+        _lib.check(_lib.lib().nmpc_policy_covariance_batch_dev(self._h, B, nc, *ins, *ptr, _stream_ptr(stream)))
+        return {k: v for k, v in res.items() if v is not None}
+
+    def policy_covariance(self, p, ubar, Xbar, K, S0, W=None, obs_var=None, want=("Sigma", "sigma_u", "sigma_g")):
+        """:meth:`policy_covariance_device` through the host entry point
+        (``nmpc_policy_covariance_batch``), NumPy arrays in the same scenario-major shapes: ``p``
+        (B,np), ``ubar`` (B,nw), ``Xbar`` (B,N+1,nx), ``K`` (B,N,nu,nx) (row-major blocks, as
+        :meth:`policy_fused` returns them) or None, ``S0`` (B,nc,nx,nx) and ``W`` (column-major
+        blocks, entries i >= j read: a symmetric matrix as it is), ``obs_var`` (B,n_obs) -- each may be
+        shared (without the B).  Returns the outputs named in ``want``."""
+        N, nu, nx = self._policy_dims()
+        if S0 is None:
+            raise ValueError("S0 is required")
+        S0 = np.ascontiguousarray(S0, dtype=np.float64)
+        if S0.ndim not in (3, 4) or S0.shape[-2:] != (nx, nx):
+            raise ValueError(f"S0: expected (nc,{nx},{nx}) or (B,nc,{nx},{nx}), got shape {S0.shape}")
+        nc = S0.shape[-3]
+        if K is not None:
+            K = np.asarray(K, dtype=np.float64)
+            if K.shape[-2:] != (nu, nx):
+                raise ValueError(f"K: expected blocks of ({nu},{nx}), got shape {K.shape}")
+            K = np.swapaxes(K, -1, -2)  # to the kernel's column-major blocks
+        fields = (("p", p, (self.np,)), ("ubar", ubar, (self.nw,)), ("Xbar", Xbar, (N + 1, nx)), ("K", K, (N, nx, nu)),
+                  ("S0", S0, (nc, nx, nx)), ("W", W, (nc, nx, nx)), ("obs_var", obs_var, (self.spec.n_obs,)))
+        arrs, B = [], None
+        for name, a, tail in fields:
+            if a is None:
+                if name in ("p", "ubar", "Xbar"):
+                    raise ValueError(f"{name} is required")
+                arrs.append((None, 0))
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape == tail:
+                arrs.append((a, 0))
+                continue
+            if a.shape[1:] != tail or B not in (None, a.shape[0]):
+                raise ValueError(f"{name}: expected {tail} or (B,) + {tail}, got shape {a.shape}")
+            B = a.shape[0]
+            arrs.append((a, int(np.prod(tail))))
+        if B is None:
+            raise ValueError("policy_covariance: no argument carries the batch size")
+        shapes = self._covariance_shapes(B, nc)
+        res = {k: np.empty(shapes[k]) for k in self.COVARIANCE_OUT if k in want}
+        if not res:
+            raise ValueError("policy_covariance: one of Sigma, sigma_u, sigma_g is required")
+        ptr = [_dptr(res[k]) if k in res else None for k in self.COVARIANCE_OUT]
+        _lib.check(_lib.lib().nmpc_policy_covariance_batch(self._h, B, nc, *_flat_ins(arrs), *ptr))
+        return res
+
     def shift_device(self, p, u_sol, w_out, v_t, w_t, stream=None):
         """Closed-loop shift on device (Python/NMPC_TT.py:13-30), see nmpc_shift_dev."""
         import torch

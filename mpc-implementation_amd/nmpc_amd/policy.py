@@ -7,7 +7,10 @@ feedforward kff_k per parameter direction and the plan's states X*_k; :func:`app
 
 with torch ops on the caller's stream: nothing is copied to the host.  :func:`rollout` runs that
 policy, clamped, on the nonlinear plant for many disturbance samples per scenario in one launch
-(``Solver.policy_rollout_device``): what it costs and whether it keeps the rows."""
+(``Solver.policy_rollout_device``): what it costs and whether it keeps the rows.  :func:`covariance`
+gives what those rollouts estimate in closed form, the state covariance around the plan and the
+standard deviation of every row and control (``Solver.policy_covariance_device``), and
+:func:`tighten` moves the bounds of the next solve inwards by a multiple of them."""
 from __future__ import annotations
 
 
@@ -106,3 +109,62 @@ def rollout_grad(solver, pol: dict, sol: dict, p, X, Jb=None, Xb=None, Ub=None, 
     if kff is not None:
         res["c_bar"] = torch.einsum("bdn,bn->bd", kff.reshape(kff.shape[0], kff.shape[1], -1), res["ubar_bar"])
     return res
+
+
+def covariance(solver, pol: dict, sol: dict, p, S0, W=None, obs_var=None, c=None, feedback: bool = True,
+               out: dict | None = None, want=("sigma_g", "sigma_u"), stream=None):
+    """The state covariance around the plan under the policy, to first order, and the standard
+    deviations of every row and every control, in one launch (``Solver.policy_covariance_device``):
+    the number :func:`rollout` estimates by sampling, without the sampling noise.  ``S0`` (B, nc, nx,
+    nx) or (nc, nx, nx) holds one covariance of the initial state per case, ``W`` likewise the process
+    noise added at every stage (None: none), ``obs_var`` (B, n_obs) or (n_obs,) the isotropic
+    variance of each obstacle's centre.  ``pol``, ``sol``, ``p``, ``c`` and ``feedback`` are
+    :func:`rollout`'s: the nominal controls are ubar = u* + sum_d kff^(d) c_d, and ``feedback=False``
+    propagates the open loop.  Returns the dict of ``Solver.policy_covariance_device``: ``sigma_g``
+    (B, nc, N+1, m), ``sigma_u`` (B, nc, N, nu) and, when asked for, ``Sigma`` (B, nc, N+1, nx, nx).
+    The gains are used as they are: where the plan holds a control on its bound, zero its row of
+    ``pol["raw"]["K"]`` first if the clamp is to count.  Nothing is copied to the host and nothing
+    synchronises."""
+    import torch
+
+    ubar = sol["x"]
+    if c is not None:
+        kff = pol["kff"]
+        if kff is None:
+            raise ValueError("the policy holds no feedforward: it was formed without directions")
+        cc = c if c.dim() == 2 else c.unsqueeze(0).expand(kff.shape[0], -1)
+        ubar = ubar + torch.einsum("bdn,bd->bn", kff.reshape(kff.shape[0], kff.shape[1], -1), cc)
+    raw = pol["raw"]
+    return solver.policy_covariance_device(p, ubar.contiguous(), raw["X"], raw["K"] if feedback else None, S0, W=W,
+                                           obs_var=obs_var, out=out, want=want, stream=stream)
+
+
+BOUND_INF = 1e19  # a bound at or beyond it is absent (IPOPT's nlp_lower / upper_bound_inf)
+
+
+def tighten(lbx, ubx, lbg, ubg, cov: dict, kappa, case: int = 0):
+    """The four bounds moved inwards by ``kappa`` standard deviations of case ``case`` of
+    :func:`covariance`'s result (``sigma_u`` for lbx / ubx, ``sigma_g`` for lbg / ubg): the bounds of
+    the next solve.  Each bound is (n,) or (B, n); the four results are (B, n).  A bound with
+    |b| >= 1e19 is absent and stays as it is; a fixed variable (lbx == ubx) and an equality row
+    (lbg == ubg) stay untouched; a pair that would cross -- the back-offs exceed the room between the
+    bounds -- collapses to its midpoint, so lower <= upper always holds (such a pair then fixes the
+    variable or the row: the room was smaller than the uncertainty asked for).  Torch ops only, on the
+    tensors' device and stream."""
+    import torch
+
+    def pair(lo, hi, sigma):
+        B = sigma.shape[0]
+        back = kappa * sigma[:, case].reshape(B, -1)
+        lo = lo.expand(B, -1) if lo.dim() == 2 else lo.unsqueeze(0).expand(B, -1)
+        hi = hi.expand(B, -1) if hi.dim() == 2 else hi.unsqueeze(0).expand(B, -1)
+        free = lo != hi
+        tl = torch.where(free & (lo.abs() < BOUND_INF), lo + back, lo)
+        th = torch.where(free & (hi.abs() < BOUND_INF), hi - back, hi)
+        mid = 0.5 * (lo + hi)
+        cross = tl > th
+        return torch.where(cross, mid, tl), torch.where(cross, mid, th)
+
+    nlx, nux = pair(lbx, ubx, cov["sigma_u"])
+    nlg, nug = pair(lbg, ubg, cov["sigma_g"])
+    return nlx, nux, nlg, nug
