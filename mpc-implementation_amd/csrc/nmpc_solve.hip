@@ -69,6 +69,13 @@ struct Params {
   int oxp[NMPC_MAX_OBS], oyp[NMPC_MAX_OBS];
   nmpc_options o;
   int nospec;  // diagnostics (NMPC_NO_SPEC=1 at nmpc_create): no speculative restoration trial pairs
+  // diagnostics (NMPC_STAGE_ROWS=1 at nmpc_create): every line-search trial forms its rows
+  // stage-parallel (eval_fg / eval_fg2) before its row pass, a pair's second rows parked in
+  // dms and copied on acceptance -- the reference run of tests/test_gpu_trial_rows.py
+  int stagerows;
+  // 65536 / m + 1: (r * mrec) >> 16 == r / m for every row index (exact while r * m < 65536;
+  // ng <= 64 * 21 and m <= 21), the row passes' stage index without an integer division
+  int mrec;
   double thv, thh;  // tan(hv), tan(hh) (host libm): the FOV tangent pairs from one tangent (NMPC_TAN2)
 };
 
@@ -157,7 +164,9 @@ constexpr Lay make_layout(int N, int m, bool lr, bool refine, bool eq) {
   if (!pin) { L.P0 = o; o += 64; L.P1 = o; o += 64; L.pv0 = o; o += 8; L.pv1 = o; o += 8; }
   L.St = o; o += 48;
   // inc: stage rows 0..N plus the -0.0 row N + 1 of the unrolled stage sums (Solver::kZeroRow)
-  L.p = o; o += 64; L.ob = o; o += al2(2 * NMPC_MAX_OBS); L.inc = o; o += al2(8 * (NS + 1));
+  // ob: the obstacle centres (x, y); the LDS-row class keeps their radius sums behind them
+  // (Solver::obr), where the trials' row passes read them with a lane-dependent index
+  L.p = o; o += 64; L.ob = o; o += al2((lr ? 3 : 2) * NMPC_MAX_OBS); L.inc = o; o += al2(8 * (NS + 1));
   if (pin) { L.P0 = L.inc; L.P1 = L.inc + 64; L.pv0 = L.inc + 128; L.pv1 = L.inc + 136; }
 #ifdef NMPC_STAMPS
   L.red = o; o += 24;  // phase timers
@@ -559,7 +568,7 @@ struct Solver {
   using KFT = std::conditional_t<CAP::lds_rows, LDS double, GLB double>;
   KFT* kf;  // k_k: LDS for the LDS-row class, workspace otherwise
   LDS double* Rc, *Rv, *Pa, *Pb, *pva, *pvb, *St;
-  LDS double* pp, *obx, *oby, *inc, *stamps;
+  LDS double* pp, *obx, *oby, *obr, *inc, *stamps;
   GLB double* filt;
   LDS int* fixm;  // fixed decision variables (lbx == ubx, make_parameter): bit c of stage k
   // uniform scalars
@@ -610,7 +619,7 @@ struct Solver {
     else kf = (KFT*)(gw + L.kf);
     Pa = sm + L.P0; Pb = sm + L.P1; pva = sm + L.pv0; pvb = sm + L.pv1;
     St = sm + L.St;
-    pp = sm + L.p; obx = sm + L.ob; oby = obx + NMPC_MAX_OBS; inc = sm + L.inc;
+    pp = sm + L.p; obx = sm + L.ob; oby = obx + NMPC_MAX_OBS; obr = oby + NMPC_MAX_OBS; inc = sm + L.inc;
     filt = gw + L.filt;
     stamps = sm + L.red;
     fixm = (LDS int*)(sm + L.fixm);
@@ -774,6 +783,27 @@ struct Solver {
     return -sqrt(ddx * ddx + ddy * ddy) + P->orr[o];
   }
 
+  // The line-search trials of the LDS-row class form their rows inside their row pass
+  // (row_scaled) instead of stage-parallel before it (eval_fg: every stage lane forms its m
+  // rows, ten square roots on N + 1 of 64 lanes, stores them, and the row pass loads them
+  // back).  Params::stagerows switches the old order back on (diagnostics).
+  static constexpr bool kRowTrials = CAP::lds_rows;
+  // dc[r] * g_r(Xs) for row r of a row-parallel pass (rows() / rows_r(): r < ng also where
+  // the trip is masked): row_value's / eval_fg's expressions.  Both row kinds are formed from
+  // clamped reads and selected, so a trip stays one basic block; the stage index comes from
+  // the multiply-shift of Params::mrec.  The distance sum is spelled as the contraction the
+  // compiler forms in eval_fg, fma(ddx, ddx, ddy * ddy): the same bits.
+  __device__ __forceinline__ double row_scaled(const LDS double* Xs, int r) const {
+    const int k = (r * P->mrec) >> 16, i = r - k * m;
+    const LDS double* xk = Xs + k * 8;
+    const int oi = i - nb;
+    const int o = oi < 0 ? 0 : (oi < NMPC_MAX_OBS ? oi : NMPC_MAX_OBS - 1);
+    const double ddx = xk[0] - obx[o], ddy = xk[1] - oby[o];
+    const double ov = -sqrt(fma(ddx, ddx, ddy * ddy)) + obr[o];
+    const double bv = xk[boxidx(i < nb ? i : 0)];
+    return dc[r] * (i < nb ? bv : ov);
+  }
+
   // f = sum_k l_k(X) and rows dst[r] = dc[r] * g_r(X) (dc may be null -> unscaled)
   // (obj = false: the rows only, f = 0 -- the restoration line search, whose trials are judged
   // without the original objective; eval_f forms it for the accepted trial alone)
@@ -843,23 +873,32 @@ struct Solver {
   // its rollout and row values formed together with the current one's (a0): the stage-
   // parallel work uses N + 1 of 64 lanes, so lanes 32 + k carry stage k of the second trial
   // in the same instructions.  Group 0 (lanes 0..31) writes Xt / dt and its increments to
-  // `inc` exactly as rollout / eval_fg do; group 1 writes its X to `lam`, its row values to
-  // `dms` and its increments to `qs` (all three dead during a line search: lam is re-formed
-  // by the next adjoint, qs by the next assembly, dms is the main phase's scratch).  Every
-  // stage's arithmetic is that of rollout / eval_fg, and the objective's wave sum of group 1
-  // sits in lanes 32..63 -- the butterfly reduces each 32-lane half in the same order, so
-  // both objectives are bitwise those of two separate calls.
+  // `inc` exactly as rollout does; group 1 writes its X to `lam` and its increments to `qs`
+  // (both dead during a line search: lam is re-formed by the next adjoint, qs by the next
+  // assembly).  Every stage's arithmetic is that of rollout.  The second trial's rows are
+  // formed from `lam` by its own row pass (trial_resto, spec 2), straight into dt.
+  // (Params::stagerows: eval_fg2 forms both trials' rows here, group 1's parked in `dms`, the
+  // main phase's scratch; the objective's wave sum of group 1 sits in lanes 32..63 -- the
+  // butterfly reduces each 32-lane half in the same order, so both objectives are bitwise
+  // those of two separate calls.)
   static constexpr bool kSpec = CAP::lds_rows && !CAP::refine && !CAP::eq && CAP::nmax <= 31;
   // Scratch of a pair's second trial: its increments in qs (stride 8, rows 0..nmax + 1, so
-  // they overwrite the S_k terms qs[k*10 + 8..9]), its X in lam, its rows in dms.  This is
-  // sound because (i) every Newton assembly rewrites qs[k*10 + 8..9] before the next
-  // factorisation reads them, and nothing else reads them between (the restoration SOC
-  // block's assemble(SUM_RESTO_SOC) writes q_k only, resolve / forward read q_k only, and
-  // the refinement that reads S_k is compiled out of the kSpec classes); (ii) between the
-  // pair's formation and a from_pair acceptance nothing writes lam or dms (the SOC block's
-  // re-solve, forward sweep, row step and spec = 0 trial write qs[0..7], dX, ds2, the
-  // *2R vectors, Xt and dt).  Bitwise check against Params::nospec:
-  // test_speculative_restoration_pairs_are_bitwise_neutral.
+  // they overwrite the S_k terms qs[k*10 + 8..9]), its X in lam.  This is sound because
+  // (i) every Newton assembly rewrites qs[k*10 + 8..9] before the next factorisation reads
+  // them, and nothing else reads them between (the restoration SOC block's
+  // assemble(SUM_RESTO_SOC) writes q_k only, resolve / forward read q_k only, and the
+  // refinement that reads S_k is compiled out of the kSpec classes); (ii) between the pair's
+  // formation and the second trial's row pass nothing writes lam (the SOC block's re-solve,
+  // forward sweep, row step and spec = 0 trials write qs[0..7], dX, ds2, the *2R vectors, Xt
+  // and dt), and that pass may overwrite dt because the first trial's rows are dead by then:
+  // a rejected trial's rows have no reader after its own row pass (which also forms the
+  // first correction's right-hand side from them, trial_resto<1>), the SOC block in between
+  // runs before the second trial is taken and its own spec = 0 trials rewrite dt anyway, and
+  // a failed SOC block or a watchdog restart read dt nowhere before the next trial's row
+  // pass rewrites all of it; only an accepted trial's rows are read later (the accept pass),
+  // and an accepted second trial's are the ones its pass has just stored.  Bitwise checks:
+  // against Params::nospec, test_speculative_restoration_pairs_are_bitwise_neutral; against
+  // Params::stagerows, tests/test_gpu_trial_rows.py.
   static_assert(!kSpec || 8 * (CAP::nmax + 2) <= 10 * (CAP::nmax + 1), "qs cannot hold a pair's increments");
   __device__ __forceinline__ void rollout2(const GLB double* Us, const GLB double* dUs, double a0, double a1,
                                            const UPre* pre = nullptr) {
@@ -2619,8 +2658,17 @@ struct Solver {
   // original objective, so the trials are formed without it and the restoration phase
   // forms it for the accepted trial alone, Solver::eval_f)
   // spec (kSpec classes): 0 this trial alone; 1 this trial and the next backtracking one
-  // (a2) formed together (rollout2 / eval_fg2); 2 this trial was formed as the second of a
-  // pair: its X in `lam`, its rows in `dms`
+  // (a2) rolled out together (rollout2); 2 this trial was formed as the second of a pair:
+  // its X waits in `lam` (under Params::stagerows also its rows, in `dms`)
+  // CM: the row pass also forms the right-hand side `cms` of the second-order correction
+  // that may follow this trial, from its own dtr - sv - pv + nv (the correction block made
+  // two row passes for that): 1 the first correction's, a (d - s - p + n) + (..), for a
+  // line search's formed trials (only its first, a = alpha_max, can be followed by a
+  // correction block, and every block is preceded by one; after any other trial cms is
+  // dead); 2 the next round's, a cms + (..), for a correction's own trial.  LDS-row class
+  // only (kCmsFold): the global-row classes keep the correction block's own two passes.
+  static constexpr bool kCmsFold = CAP::lds_rows;
+  template <int CM = 0>
   __device__ __forceinline__ bool trial_resto(double a, const GLB double* dUs, const RV* dss,
                                               const GLB double* dps, const GLB double* dns, double& fo,
                                               double& phit, double& tht, int spec = 0, double a2 = 0.0,
@@ -2647,55 +2695,69 @@ struct Solver {
     XSTAMP1(_x0, X_TCTRL);
     bool bad = false;
     // theta_R, the barrier sums and the p/n sums in one pass over the rows
-    auto rowpass = [&](auto dtv) {
+    // (dtv: the rows' values where a stage-parallel phase formed them, Params::stagerows;
+    // Xf: the trial's X, from which the pass forms them itself and stores them to dt)
+    auto rowpass = [&](auto dtv, const LDS double* Xf = nullptr) {
       rows_r([&](int r, bool on) {
         const double sv = s[r] + a * dss[r], pv = pR[r] + a * dps[r], nv = nR[r] + a * dns[r];
-        const double dtr = dtv[r];
+        double dtr;
+        if constexpr (std::is_same_v<decltype(dtv), std::nullptr_t>) {
+          dtr = row_scaled(Xf, r);
+          if (on) dt[r] = dtr;
+        } else {
+          dtr = dtv[r];
+        }
         barrier_row(r, on, sv, logs, damp);
         la.mul2(on ? pv : 1.0, on ? nv : 1.0);
+        const double cv = dtr - sv - pv + nv;
+        if constexpr (CM == 1 && kCmsFold) {
+          const double c0 = d[r] - s[r] - pR[r] + nR[r];
+          const double cn = a * c0 + cv;
+          if (on) cms[r] = cn;
+        } else if constexpr (CM == 2 && kCmsFold) {
+          const double cn = a * cms[r] + cv;
+          if (on) cms[r] = cn;
+        }
         if (on) {
-          th += fabs(dtr - sv - pv + nv);
+          th += fabs(cv);
           if (!isfinite(dtr)) bad = true;
           pn += pv + nv;
         }
       });
     };
-    bool done = false;
-    if constexpr (kSpec) {
-      if (spec == 2) {
-        fo = 0.0;
-        XSTAMP0(_x3);
-        rowpass(dms);
-        XSTAMP1(_x3, X_TROWS);
-        done = true;
-      } else if (spec == 1) {
-        XSTAMP0(_x1);
-        rollout2(U, dUs, a, a2, &up);
-        XSTAMP1(_x1, X_TROLL);
-        XSTAMP0(_x2);
-        double f0, f1;
-        eval_fg2(f0, f1, false);
-        fo = 0.0;
-        *fo2 = 0.0;
-        XSTAMP1(_x2, X_TEVAL);
-        XSTAMP0(_x3);
-        rowpass(dt);
-        XSTAMP1(_x3, X_TROWS);
-        done = true;
-      }
-    }
-    if (!done) {
+    // the stage-parallel part: the rollout(s), and under Params::stagerows the rows
+    const bool stage_rows = !kRowTrials || P->stagerows;
+    const bool second = kSpec && spec == 2, pair = kSpec && spec == 1;
+    fo = 0.0;
+    if (!second) {
       XSTAMP0(_x1);
-      rollout(U, Xt, dUs, a, &up);
+      if constexpr (kSpec) {
+        if (pair) rollout2(U, dUs, a, a2, &up);
+        else rollout(U, Xt, dUs, a, &up);
+      } else {
+        rollout(U, Xt, dUs, a, &up);
+      }
       XSTAMP1(_x1, X_TROLL);
       XSTAMP0(_x2);
-      fo = 0.0;
-      eval_fg(Xt, dt, dc, false);
+      if (pair) *fo2 = 0.0;
+      if (stage_rows) {
+        bool both = false;
+        if constexpr (kSpec) {
+          if (pair) {
+            double f0, f1;
+            eval_fg2(f0, f1, false);
+            both = true;
+          }
+        }
+        if (!both) eval_fg(Xt, dt, dc, false);
+      }
       XSTAMP1(_x2, X_TEVAL);
-      XSTAMP0(_x3);
-      rowpass(dt);
-      XSTAMP1(_x3, X_TROWS);
     }
+    XSTAMP0(_x3);
+    if (!stage_rows) rowpass(nullptr, second ? lam : Xt);
+    else if (second) rowpass(dms);
+    else rowpass(dt);
+    XSTAMP1(_x3, X_TROWS);
     XSTAMP0(_x4);
     tht = wsum(th);
     if (wany(bad)) return false;
@@ -2900,17 +2962,33 @@ struct Solver {
     });
     sync();
     rollout(U, Xt, dUs, a, &up);
-    ft = df * eval_fg(Xt, dt, dc);
-    // theta and the barrier sums in one pass over the rows
+    // theta and the barrier sums in one pass over the rows; FORM: the pass forms the trial's
+    // row values itself and stores them to dt (kRowTrials), otherwise it reads eval_fg's
     bool bad = false;
-    rows([&](int r, bool on) {
-      const double sv = s[r] + a * dss[r], dtr = dt[r];
-      barrier_row(r, on, sv, logs, damp);
-      if (on) {
-        th += fabs(dtr - sv);
-        if (!isfinite(dtr)) bad = true;
-      }
-    });
+    auto rowpass = [&](auto form) {
+      rows([&](int r, bool on) {
+        const double sv = s[r] + a * dss[r];
+        double dtr;
+        if constexpr (decltype(form)::value) {
+          dtr = row_scaled(Xt, r);
+          if (on) dt[r] = dtr;
+        } else {
+          dtr = dt[r];
+        }
+        barrier_row(r, on, sv, logs, damp);
+        if (on) {
+          th += fabs(dtr - sv);
+          if (!isfinite(dtr)) bad = true;
+        }
+      });
+    };
+    if (kRowTrials && !P->stagerows) {
+      ft = df * eval_f(Xt, tc);  // eval_fg's f: same lanes, same wave sum, same cache writes
+      rowpass(std::true_type{});
+    } else {
+      ft = df * eval_fg(Xt, dt, dc);
+      rowpass(std::false_type{});
+    }
     tht = wsum(th);
     bad = wany(bad) || !isfinite(ft);
     if (bad) return false;
@@ -3373,7 +3451,7 @@ __device__ __forceinline__ void resto_phase(const Params* __restrict__ prm, doub
         a = rskip ? V[18] * o.alpha_red_factor : V[18];
         nsteps = 0;
         // speculative pairs (Solver::kSpec): each trial not formed yet is formed together
-        // with the next backtracking trial (spec_a), whose X / rows wait in lam / dms
+        // with the next backtracking trial (spec_a), whose X waits in lam
         double spec_a = -1.0, spec_f = 0.0;
         // (Params::nospec, a diagnostic: every trial formed alone -- the reference run of the
         // bitwise test of the pairs, test_speculative_restoration_pairs_are_bitwise_neutral)
@@ -3387,21 +3465,23 @@ __device__ __forceinline__ void resto_phase(const Params* __restrict__ prm, doub
             spec_a = -1.0;
           } else {
             const double an = a * o.alpha_red_factor;
-            ok_t = S.trial_resto(a, S.dU, S.ds, S.dpR, S.dnR, fo_t, ph, th, spec_on ? 1 : 0, an, &spec_f);
+            ok_t = S.template trial_resto<1>(a, S.dU, S.ds, S.dpR, S.dnR, fo_t, ph, th, spec_on ? 1 : 0, an, &spec_f);
             spec_a = spec_on ? an : -1.0;
           }
           if (ok_t && r_check(a, ph, th)) {
             acc = 1; V[19] = a; V[20] = fo_t; V[21] = ph; a_test = a;
             tcb_acc = from_pair ? 1 : 0;
-            if (from_pair) {  // the accepted trial's X and rows into Xt / dt for the accept
-              if (S.lanef() <= N) {
+            if (from_pair) {  // the accepted trial's X into Xt for the accept (its row pass put its
+              if (S.lanef() <= N) {  // rows into dt; under Params::stagerows they wait in dms)
 #pragma unroll
                 for (int c = 0; c < 8; ++c) S.Xt[S.lanef() * 8 + c] = S.lam[S.lanef() * 8 + c];
               }
-              S.rows([&](int r, bool on) {
-                const double v = S.dms[r];
-                if (on) S.dt[r] = v;
-              });
+              if (!Solver<CAP>::kRowTrials || prm->stagerows) {
+                S.rows([&](int r, bool on) {
+                  const double v = S.dms[r];
+                  if (on) S.dt[r] = v;
+                });
+              }
               sync();
             }
             break;
@@ -3409,8 +3489,13 @@ __device__ __forceinline__ void resto_phase(const Params* __restrict__ prm, doub
           if (ok_t && a == V[18] && V[15] <= th && o.max_soc > 0) {
             RSTAMP0(_soc);
             XSTAMP0(_xsb);
+            // (the corrections' right-hand side cms = a cms + (dt - s - p + n at the last trial),
+            // from d - s - p + n: formed by the row pass of the trial before each round,
+            // trial_resto<1> above and <2> below; the global-row classes form it here)
             double th_tr = th, th_old = 0.0, a_soc = a;
-            for (int r = S.lanef(); r < ng; r += WAVE) S.cms[r] = S.d[r] - S.s[r] - S.pR[r] + S.nR[r];
+            if constexpr (!Solver<CAP>::kCmsFold) {
+              for (int r = S.lanef(); r < ng; r += WAVE) S.cms[r] = S.d[r] - S.s[r] - S.pR[r] + S.nR[r];
+            }
             sync();
             const auto* dsp = S.ds;
             const GLB double *dpp = S.dpR, *dnp = S.dnR;
@@ -3418,13 +3503,15 @@ __device__ __forceinline__ void resto_phase(const Params* __restrict__ prm, doub
             bool soc_ok = false;
             while (cnt < o.max_soc && (cnt == 0 || th_tr <= o.kappa_soc * th_old)) {
               th_old = th_tr;
-              XSTAMP0(_xs1);
-              for (int r = S.lanef(); r < ng; r += WAVE) {
-                const double sv = S.s[r] + a_soc * dsp[r], pv = S.pR[r] + a_soc * dpp[r], nv = S.nR[r] + a_soc * dnp[r];
-                S.cms[r] = a_soc * S.cms[r] + (S.dt[r] - sv - pv + nv);
+              if constexpr (!Solver<CAP>::kCmsFold) {
+                XSTAMP0(_xs1);
+                for (int r = S.lanef(); r < ng; r += WAVE) {
+                  const double sv = S.s[r] + a_soc * dsp[r], pv = S.pR[r] + a_soc * dpp[r], nv = S.nR[r] + a_soc * dnp[r];
+                  S.cms[r] = a_soc * S.cms[r] + (S.dt[r] - sv - pv + nv);
+                }
+                sync();
+                XSTAMP1(_xs1, X_SCMS);
               }
-              sync();
-              XSTAMP1(_xs1, X_SCMS);
               XSTAMP0(_xs2);
               S.assemble(SUM_RESTO_SOC, 0.0, 0.0, true);
               XSTAMP1(_xs2, X_SASM);
@@ -3447,7 +3534,7 @@ __device__ __forceinline__ void resto_phase(const Params* __restrict__ prm, doub
               a_soc = wmin(ap);
               dsp = S.ds2; dpp = S.dp2R; dnp = S.dn2R;
               double fo2, ph2, th2;
-              if (!S.trial_resto(a_soc, S.dU2, S.ds2, S.dp2R, S.dn2R, fo2, ph2, th2)) break;
+              if (!S.template trial_resto<2>(a_soc, S.dU2, S.ds2, S.dp2R, S.dn2R, fo2, ph2, th2)) break;
               if (r_check(a, ph2, th2)) {
                 acc = 2; V[19] = a_soc; V[20] = fo2; V[21] = ph2; a_test = a; soc_ok = true;
                 break;
@@ -3668,6 +3755,9 @@ __device__ __forceinline__ int solve_one(Solver<CAP>& S, const Params* __restric
   if (S.lanef() < S.nobs) {
     S.obx[S.lanef()] = prm->oxp[S.lanef()] >= 0 ? S.pp[prm->oxp[S.lanef()]] : prm->ox[S.lanef()];
     S.oby[S.lanef()] = prm->oyp[S.lanef()] >= 0 ? S.pp[prm->oyp[S.lanef()]] : prm->oy[S.lanef()];
+  }
+  if constexpr (Solver<CAP>::kRowTrials) {  // every entry: the row passes' clamped reads stay finite
+    if (S.lanef() < NMPC_MAX_OBS) S.obr[S.lanef()] = prm->orr[S.lanef()];
   }
   if (S.lanef() == 0) {  // cost weights (LDS scalar slots 30, 31)
     S.rvars[30] = prm->w1p >= 0 ? S.pp[prm->w1p] : prm->w1;
@@ -5373,6 +5463,8 @@ int nmpc_create(const nmpc_desc* desc, nmpc_handle** out) {
   }
   P.o = desc->opts;
   if (const char* e = std::getenv("NMPC_NO_SPEC")) P.nospec = std::atoi(e) != 0;
+  if (const char* e = std::getenv("NMPC_STAGE_ROWS")) P.stagerows = std::atoi(e) != 0;
+  P.mrec = 65536 / P.m + 1;  // (m >= 2: the box rows)
   {
     int ldsd = 0;
     const bool forcedE = pick_class(P, &h->kern, &h->loop, &h->sched, &ldsd, &h->ws_doubles);
