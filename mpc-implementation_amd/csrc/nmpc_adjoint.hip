@@ -14,9 +14,10 @@
 // Execution model: the products kernels'.  One wavefront per (scenario, seed chunk), stage k on
 // lane k, rows and variables strided over the lanes, control flow wave-uniform.
 // Once per wavefront:
-//   1. scenario data, rollout and stage costs as nmpc_products_kernel;
+//   1. scenario data, rollout and stage costs (load_params, load_controls, point_rollout of
+//      nmpc_eval_shared.hip);
 //   2. where a cost weight comes from p and a z seed will ask for it: the stage-cost gradients
-//      with the weights (1, 0) and (0, 1), kept by lane k (as nmpc_pproducts_kernel);
+//      with the weights (1, 0) and (0, 1), kept by lane k (unit_weight_grads);
 //   3. derivs<true, true>: gl, Hl; adjoint(obj_factor, lam_g): lam_{k+1};
 //   4. lane k keeps for every seed: obj_factor Hl_k (21 packed entries), the summed obstacle
 //      curvature sum_o lam_{k,o} Hg_o, the dynamics terms d33, d34, d44, s03, s04 of
@@ -24,7 +25,7 @@
 //      obstacle's own lam_{k,o} Hg_o goes to the workspace where its centre comes from p.
 // Per seed (reverse over forward; a NULL seed's terms are not formed):
 //   5. z given: the forward tangent xi_0 = 0, xi_{k+1} = A_k xi_k + B_k z_k as in-order prefix
-//      sums (nmpc_products_kernel's step 4), kept by lane k in registers;
+//      sums (nmpc_products_kernel's step 4: a copy), kept by lane k in registers;
 //   6. the stage source s_k without its row part, into the gradient slice of the workspace:
 //        Xb_k + obj_factor Hl_k xi_k + sum_o lam_{k,o} Hg_o xi_k + d2_xx(lam_{k+1}^T T f) xi_k
 //             + Hxu_k z_k
@@ -44,21 +45,12 @@
 
 namespace {
 
-static_assert(CapA::L.wstotal >= kAdjWs && CapB::L.wstotal >= kAdjWs && CapC::L.wstotal >= kAdjWs &&
-                  CapD::L.wstotal >= kAdjWs && CapA32::L.wstotal >= kAdjWs && CapC32::L.wstotal >= kAdjWs &&
-                  CapE::L.wstotal >= kAdjWs,
+static_assert(fits_every_class(kAdjWs),
               "a solver class's workspace is smaller than one wavefront's of the adjoint-products kernel");
 
-// LDS carve-up (doubles)
-constexpr int R_PP = 0;                       // p, internal layout (<= 64)
-constexpr int R_OB = R_PP + 64;               // obstacle x (16), y (16)
-constexpr int R_RV = R_OB + 2 * NMPC_MAX_OBS; // Solver::rvars; [30], [31] = cost weights
-constexpr int R_ST = R_RV + 32;               // phase-timer slots (NMPC_STAMPS builds write them)
-constexpr int R_X = R_ST + PH_COUNT;          // trajectory, 8 per stage
-constexpr int R_TRIG = R_X + 8 * NS;
-constexpr int R_INC = R_TRIG + 8 * NS;        // prefix / suffix sum scratch
-constexpr int R_LAM = R_INC + 8 * NS;         // lam, then each seed's nu
-constexpr int R_CR = R_LAM + 8 * NS;          // the seed's Hxu_k^T xi_k
+// LDS carve-up (doubles): the unit's head (its multipliers' buffer holds lam, then each seed's
+// nu), then
+constexpr int R_CR = B_END;                   // the seed's Hxu_k^T xi_k
 constexpr int R_TOTAL = R_CR + NS;
 static_assert(R_TOTAL * 8 <= 32 * 1024, "adjoint-products kernel LDS");
 
@@ -70,87 +62,37 @@ __global__ __launch_bounds__(WAVE) void nmpc_adjoint_kernel(const Params* __rest
   Solver<CapEv> S{};
   LDS double* sm = (LDS double*)smem;
   GLB double* gw = (GLB double*)(io.ws + ((long long)b * chunks + chunk) * kAdjWs);
-  S.P = (const CST Params*)prm; S.sm = sm; S.lane_ = threadIdx.x; S.b = b;
-  S.N = prm->N; S.m = prm->m; S.nobs = prm->nobs; S.nw = prm->nw; S.ng = prm->ng; S.T = prm->T;
-  S.nb = prm->nb; S.nuE = prm->nuE; S.nwE = prm->nwE;
-  S.U = gw + kProdU; S.gl = gw + kProdGl; S.Hl = gw + kProdHl; S.tc = gw + kProdTc; S.dc = gw + kProdDc;
-  S.pp = sm + R_PP; S.obx = sm + R_OB; S.oby = S.obx + NMPC_MAX_OBS; S.rvars = sm + R_RV; S.stamps = sm + R_ST;
-  S.X = sm + R_X; S.trig = sm + R_TRIG; S.inc = sm + R_INC; S.lam = sm + R_LAM;
+  bind_solver(S, prm, sm, gw, b, kProdU, kProdGl, kProdHl, kProdTc, kProdDc);
   GLB double* oc = gw + kPprodOc;
   LDS double* cr = sm + R_CR;
-  const int N = S.N, m = S.m, nb = S.nb, nw = S.nw, ng = S.ng, nwE = S.nwE, np = prm->np, npE = prm->npE;
+  const int N = S.N, m = S.m, nb = S.nb, ng = S.ng, nwE = S.nwE, np = prm->np, npE = prm->npE;
   const int nxE = prm->nxE, nXE = nxE * (N + 1);
   const int w1p = prm->w1p, w2p = prm->w2p;
   const double sig = io.obj_factor;
   const double T = S.T;
   const int lane = S.lanef();
   const double* yb = io.lam_g ? io.lam_g + (long long)b * io.ld_lam_g : nullptr;
-  const double* xb = io.x + (long long)b * io.ld_x;
   const double* ys = io.y ? io.y + (long long)b * io.ld_y : nullptr;
   const double* zs = io.z ? io.z + (long long)b * io.ld_z : nullptr;
   const double* Xs = io.Xb ? io.Xb + (long long)b * io.ld_Xb : nullptr;
   const bool zp = zs && io.pbar;  // the p-side terms of a z seed are asked for
 
-  // ---------------- scenario data (as nmpc_products_kernel loads it)
-  if (lane < PH_COUNT) S.stamps[lane] = 0.0;
-  for (int i = lane; i < np; i += WAVE) {
-    const int e = ext_p(prm, i);
-    S.pp[i] = e >= 0 ? io.p[(long long)b * io.ld_p + e] : 0.0;
-  }
+  // ---------------- scenario data, rollout and stage costs
+  load_params(S, prm, lane, io.p + (long long)b * io.ld_p);
+  load_controls(S, prm, lane, io.x + (long long)b * io.ld_x, true);
   sync();
-  if (lane < NMPC_MAX_OBS) {
-    const bool on = lane < S.nobs;
-    S.obx[lane] = on ? (prm->oxp[lane] >= 0 ? S.pp[prm->oxp[lane]] : prm->ox[lane]) : 0.0;
-    S.oby[lane] = on ? (prm->oyp[lane] >= 0 ? S.pp[prm->oyp[lane]] : prm->oy[lane]) : 0.0;
-  }
-  if (lane == 0) {
-    S.rvars[30] = w1p >= 0 ? S.pp[w1p] : prm->w1;
-    S.rvars[31] = w2p >= 0 ? S.pp[w2p] : prm->w2;
-  }
-  for (int i = lane; i < nw; i += WAVE) {
-    const int e = ext_u(prm, i);
-    S.U[i] = e >= 0 ? xb[e] : 0.0;
-  }
-  for (int r = lane; r < ng; r += WAVE) S.dc[r] = 1.0;  // unscaled rows
-  sync();
-
-  // ---------------- rollout and stage costs (their transcendentals)
-  S.rollout(S.U, S.X);
-  if (lane < N) (void)S.stage_cost(S.X + lane * 8, S.tc + lane * 12);
-  sync();
+  point_rollout(S, lane);
 
   const int k = lane;
   const bool stage = k >= 1 && k <= N;  // the stages whose state depends on w
   const int sv[6] = {0, 1, 2, 5, 6, 7};  // the states a stage cost reads
 
-  // ---------------- cost weights from p: unit-weight gradients, lane k stage k's
-  double g10[6], g01[6];
+  // ---------------- cost weights from p: unit-weight gradients ((1, 0): gu[0:6], (0, 1):
+  // gu[6:12]), lane k stage k's
+  double gu[12];
 #pragma unroll
-  for (int a = 0; a < 6; ++a) g10[a] = g01[a] = 0.0;
-  if (zp && (w1p >= 0 || w2p >= 0)) {
-    const double w1s = S.rvars[30], w2s = S.rvars[31];
-    sync();
-    if (w1p >= 0) {
-      if (lane == 0) { S.rvars[30] = 1.0; S.rvars[31] = 0.0; }
-      sync();
-      S.derivs<false, true>(S.X, S.U, S.tc);
-      if (k < N) {
-#pragma unroll
-        for (int a = 0; a < 6; ++a) g10[a] = S.gl[k * 8 + sv[a]];
-      }
-    }
-    if (w2p >= 0) {
-      if (lane == 0) { S.rvars[30] = 0.0; S.rvars[31] = 1.0; }
-      sync();
-      S.derivs<false, true>(S.X, S.U, S.tc);
-      if (k < N) {
-#pragma unroll
-        for (int a = 0; a < 6; ++a) g01[a] = S.gl[k * 8 + sv[a]];
-      }
-    }
-    if (lane == 0) { S.rvars[30] = w1s; S.rvars[31] = w2s; }
-    sync();
-  }
+  for (int a = 0; a < 12; ++a) gu[a] = 0.0;
+  if (zp) unit_weight_grads(S, prm, lane, [&](int s, double g) { gu[s] = g; });
 
   // ---------------- derivatives and multipliers at the scenario's own weights
   S.derivs<true, true>(S.X, S.U, S.tc);
@@ -163,38 +105,26 @@ __global__ __launch_bounds__(WAVE) void nmpc_adjoint_kernel(const Params* __rest
   for (int t = 0; t < 21; ++t) Hc[t] = 0.0;
   double q00 = 0.0, q01 = 0.0, q11 = 0.0;
   double d33 = 0.0, d34 = 0.0, d44 = 0.0, s03 = 0.0, s04 = 0.0;
-  double E03 = 0.0, E04 = 0.0, E13 = 0.0, E14 = 0.0, E23 = 0.0, b00 = 0.0, b10 = 0.0, b20 = 0.0;
-  if (k < N) S.stage_AB(k, E03, E04, E13, E14, E23, b00, b10, b20);
+  const StageAB ab = point_stage_ab(S, k);
   if (zs) {
     if (stage) {
 #pragma unroll
       for (int t = 0; t < 21; ++t) Hc[t] = sig * S.Hl[k * 21 + t];
-      if (yb) {  // y-weighted obstacle curvature: nmpc_products_kernel's, rows in order
-        const LDS double* xk = S.X + k * 8;
+      if (yb) {  // y-weighted obstacle curvature, rows in order, over the stages k >= 1 alone
         for (int o = 0; o < S.nobs; ++o) {
-          const double C = yb[k * m + nb + o];
-          const double ddx = xk[0] - S.obx[o], ddy = xk[1] - S.oby[o];
-          const double idd = rsq(ddx * ddx + ddy * ddy);
-          const double id3 = idd * idd * idd;
-          const double h00 = C * (-ddy * ddy * id3), h01 = C * (ddx * ddy * id3), h11 = C * (-ddx * ddx * id3);
-          q00 += h00; q01 += h01; q11 += h11;
+          const ObsCurv h = obstacle_curvature(S, k, o, yb[k * m + nb + o]);
+          q00 += h.h00; q01 += h.h01; q11 += h.h11;
           if (io.pbar && (prm->oxp[o] >= 0 || prm->oyp[o] >= 0)) {
             GLB double* q = oc + (k * NMPC_MAX_OBS + o) * 3;
-            q[0] = h00; q[1] = h01; q[2] = h11;
+            q[0] = h.h00; q[1] = h.h01; q[2] = h.h11;
           }
         }
       }
     }
-    if (k < N) {  // second derivatives of lam_{k+1}^T T f(x_k, u_k): Solver::assemble's dyn branch
-      const LDS double* tg = S.trig + k * 8;
-      const double ct = tg[0], stt = tg[1], cp = tg[2], sp = tg[3], v = tg[4];
-      const LDS double* ln = S.lam + (k + 1) * 8;
-      const double l0 = ln[0], l1 = ln[1], l2 = ln[2];
-      d33 = T * (-l0 * v * cp * ct - l1 * v * sp * ct - l2 * v * stt);
-      d44 = T * (-l0 * v * cp * ct - l1 * v * sp * ct);
-      d34 = T * (l0 * v * sp * stt - l1 * v * cp * stt);
-      s03 = T * (-l0 * cp * stt - l1 * sp * stt + l2 * ct);
-      s04 = T * (-l0 * sp * ct + l1 * cp * ct);
+    if (k < N) {
+      const Dyn2 e = point_dyn2(S, k);
+      d33 = T * e.e33; d44 = T * e.e44; d34 = T * e.e34;
+      s03 = T * e.e03; s04 = T * e.e04;
     }
   }
   // the internal entry of p this lane forms, and its place in the caller's layout
@@ -226,9 +156,9 @@ __global__ __launch_bounds__(WAVE) void nmpc_adjoint_kernel(const Params* __rest
           for (int c = 0; c < 5; ++c) dx[3 + c] = dx[3 + c] + S.inc[j * 8 + c];
         }
         if (k < N) {  // stage 0: xi_0 = 0, only B_0 z_0
-          S.inc[k * 8 + 5] = k == 0 ? b00 * du0 : (E03 * dx[3] + E04 * dx[4]) + b00 * du0;
-          S.inc[k * 8 + 6] = k == 0 ? b10 * du0 : (E13 * dx[3] + E14 * dx[4]) + b10 * du0;
-          S.inc[k * 8 + 7] = k == 0 ? b20 * du0 : E23 * dx[3] + b20 * du0;
+          S.inc[k * 8 + 5] = k == 0 ? ab.b00 * du0 : (ab.E03 * dx[3] + ab.E04 * dx[4]) + ab.b00 * du0;
+          S.inc[k * 8 + 6] = k == 0 ? ab.b10 * du0 : (ab.E13 * dx[3] + ab.E14 * dx[4]) + ab.b10 * du0;
+          S.inc[k * 8 + 7] = k == 0 ? ab.b20 * du0 : ab.E23 * dx[3] + ab.b20 * du0;
         }
       }
       sync();
@@ -288,16 +218,7 @@ __global__ __launch_bounds__(WAVE) void nmpc_adjoint_kernel(const Params* __rest
     if (yd) S.adjoint(1.0, yd);
     else S.adjoint(1.0, (const double*)nullptr);
     // 8. wbar
-    if (io.wbar) {
-      double* o = io.wbar + ((long long)b * io.na + d) * nwE;
-      for (int i = lane; i < nw; i += WAVE) {
-        const int e = ext_u(prm, i);
-        if (e < 0) continue;
-        const int kk = i / 6;
-        const double g = S.grad_u(i);
-        o[e] = (zd && i == 6 * kk && kk >= 1) ? g + cr[kk] : g;
-      }
-    }
+    if (io.wbar) put_grad_u(S, prm, lane, cr, zd != nullptr, false, io.wbar + ((long long)b * io.na + d) * nwE);
     // 9. pbar
     if (io.pbar) {
       double v = lane < 8 ? S.lam[lane] : 0.0;
@@ -309,14 +230,14 @@ __global__ __launch_bounds__(WAVE) void nmpc_adjoint_kernel(const Params* __rest
         if (w1p >= 0) {
           double a_ = 0.0;
 #pragma unroll
-          for (int a = 0; a < 6; ++a) a_ += g10[a] * dx[sv[a]];
+          for (int a = 0; a < 6; ++a) a_ += gu[a] * dx[sv[a]];
           const double s = sig * wsum(stage ? a_ : 0.0);
           if (lane == w1p) v += s;
         }
         if (w2p >= 0) {
           double a_ = 0.0;
 #pragma unroll
-          for (int a = 0; a < 6; ++a) a_ += g01[a] * dx[sv[a]];
+          for (int a = 0; a < 6; ++a) a_ += gu[6 + a] * dx[sv[a]];
           const double s = sig * wsum(stage ? a_ : 0.0);
           if (lane == w2p) v += s;
         }

@@ -37,22 +37,18 @@ using CapEv = CapC;
 static_assert(CapEv::nmax == NMPC_MAX_N && CapEv::mmax == 5 + NMPC_MAX_OBS && !CapEv::lds_rows,
               "the evaluation kernel instantiates the any-shape, global-row class");
 static_assert(!Solver<CapEv>::kUnrollStages, "no -0.0 row in this kernel's stage scratch");
-static_assert(CapA::L.wstotal >= kEvalWs && CapB::L.wstotal >= kEvalWs && CapC::L.wstotal >= kEvalWs &&
-                  CapD::L.wstotal >= kEvalWs && CapA32::L.wstotal >= kEvalWs && CapC32::L.wstotal >= kEvalWs &&
-                  CapE::L.wstotal >= kEvalWs,
-              "a solver class's workspace is smaller than the evaluation's");
 
-// LDS carve-up (doubles)
-constexpr int NS = kEvalStages;
-constexpr int E_PP = 0;                       // p, internal layout (<= 64)
-constexpr int E_OB = E_PP + 64;               // obstacle x (16), y (16)
-constexpr int E_RV = E_OB + 2 * NMPC_MAX_OBS; // Solver::rvars; [30], [31] = cost weights
-constexpr int E_ST = E_RV + 32;               // phase-timer slots (NMPC_STAMPS builds write them)
-constexpr int E_X = E_ST + PH_COUNT;          // trajectory, 8 per stage
-constexpr int E_TRIG = E_X + 8 * NS;
-constexpr int E_INC = E_TRIG + 8 * NS;        // rollout increments / adjoint scratch
-constexpr int E_LAM = E_INC + 8 * NS;
-constexpr int E_GF = E_LAM + 8 * NS;          // grad f, 6 per stage (internal layout)
+}  // namespace
+
+// what the kernels of this unit share (no kernel of its own)
+#include "nmpc_eval_shared.hip"
+
+namespace {
+
+static_assert(fits_every_class(kEvalWs), "a solver class's workspace is smaller than the evaluation's");
+
+// LDS carve-up (doubles): the unit's head, then
+constexpr int E_GF = B_END;                   // grad f, 6 per stage (internal layout)
 constexpr int E_GL = E_GF + 6 * NS;           // grad of the Lagrangian
 constexpr int E_TOTAL = E_GL + 6 * NS;
 static_assert(E_TOTAL * 8 <= 32 * 1024, "evaluation kernel LDS");
@@ -90,13 +86,8 @@ __global__ __launch_bounds__(WAVE) void nmpc_eval_kernel(const Params* __restric
   Solver<CapEv> S{};
   LDS double* sm = (LDS double*)smem;
   GLB double* gw = (GLB double*)(io.ws + (long long)b * kEvalWs);
-  S.P = (const CST Params*)prm; S.sm = sm; S.lane_ = threadIdx.x; S.b = b;
-  S.N = prm->N; S.m = prm->m; S.nobs = prm->nobs; S.nw = prm->nw; S.ng = prm->ng; S.T = prm->T;
-  S.nb = prm->nb; S.nuE = prm->nuE; S.nwE = prm->nwE;
-  S.U = gw + kEvalU; S.gl = gw + kEvalGl; S.Hl = S.gl /* never written: derivs<false> */; S.tc = gw + kEvalTc;
-  S.dc = gw + kEvalDc;
-  S.pp = sm + E_PP; S.obx = sm + E_OB; S.oby = S.obx + NMPC_MAX_OBS; S.rvars = sm + E_RV; S.stamps = sm + E_ST;
-  S.X = sm + E_X; S.trig = sm + E_TRIG; S.inc = sm + E_INC; S.lam = sm + E_LAM;
+  // (Hl on gl: never written, derivs<false>)
+  bind_solver(S, prm, sm, gw, b, kEvalU, kEvalGl, kEvalGl, kEvalTc, kEvalDc);
   LDS double* gF = sm + E_GF;
   LDS double* gL = sm + E_GL;
   const int N = S.N, m = S.m, nw = S.nw, ng = S.ng, nwE = S.nwE;
@@ -106,28 +97,9 @@ __global__ __launch_bounds__(WAVE) void nmpc_eval_kernel(const Params* __restric
   const double* lxb = io.lam_x ? io.lam_x + (long long)b * io.ld_lam_x : nullptr;
   const double* xb = io.x + (long long)b * io.ld_x;
 
-  // ---------------- scenario data (as solve_one loads it)
-  if (lane < PH_COUNT) S.stamps[lane] = 0.0;
-  for (int i = lane; i < prm->np; i += WAVE) {
-    const int e = ext_p(prm, i);
-    S.pp[i] = e >= 0 ? io.p[(long long)b * io.ld_p + e] : 0.0;
-  }
-  sync();
-  if (lane < NMPC_MAX_OBS) {
-    const bool on = lane < S.nobs;
-    S.obx[lane] = on ? (prm->oxp[lane] >= 0 ? S.pp[prm->oxp[lane]] : prm->ox[lane]) : 0.0;
-    S.oby[lane] = on ? (prm->oyp[lane] >= 0 ? S.pp[prm->oyp[lane]] : prm->oy[lane]) : 0.0;
-  }
-  if (lane == 0) {
-    S.rvars[30] = prm->w1p >= 0 ? S.pp[prm->w1p] : prm->w1;
-    S.rvars[31] = prm->w2p >= 0 ? S.pp[prm->w2p] : prm->w2;
-  }
-  for (int i = lane; i < nw; i += WAVE) {
-    const int e = ext_u(prm, i);
-    S.U[i] = e >= 0 ? xb[e] : 0.0;
-  }
-  if (want_grad && yb)
-    for (int r = lane; r < ng; r += WAVE) S.dc[r] = 1.0;  // unscaled rows
+  // ---------------- scenario data
+  load_params(S, prm, lane, io.p + (long long)b * io.ld_p);
+  load_controls(S, prm, lane, xb, want_grad && yb);
   sync();
 
   // ---------------- X, f, g
@@ -151,13 +123,7 @@ __global__ __launch_bounds__(WAVE) void nmpc_eval_kernel(const Params* __restric
     const double fs = wsum(f);
     if (lane == 0 && io.f) io.f[b] = fs;
   }
-  if (io.X) {
-    const int nxE = prm->nxE, nXE = nxE * (N + 1);
-    for (int i = lane; i < prm->nX; i += WAVE) {
-      const int k = i >> 3, c = i & 7;
-      if (c < nxE) io.X[(long long)b * nXE + k * nxE + c] = S.X[i];
-    }
-  }
+  if (io.X) put_trajectory(prm, lane, S.X, io.X + (long long)b * (prm->nxE * (N + 1)));
   if (!want_grad) return;
 
   // ---------------- gradients: objective, then Lagrangian

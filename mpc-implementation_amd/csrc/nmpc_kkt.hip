@@ -16,8 +16,9 @@
 //
 // Execution model: the solver's.  One wavefront per scenario, fp64, control flow wave-uniform.
 // Once per wavefront:
-//   1. scenario data, rollout and stage costs as nmpc_products_kernel (the stage costs fill
-//      the transcendental cache that derivs<true, true> reads);
+//   1. scenario data, rollout and stage costs (load_params, load_controls, point_rollout of
+//      nmpc_eval_shared.hip: the stage costs fill the transcendental cache that
+//      derivs<true, true> reads);
 //   2. the weights: sigma_x into the kernel's 6-per-stage layout (+inf: the variable is fixed,
 //      Solver::fixm, as make_parameter's), sigma_s and delta checked; an invalid weight ends
 //      the scenario with info = -11 and NaN outputs;
@@ -38,36 +39,20 @@
 
 namespace {
 
-static_assert(CapA::L.wstotal >= kKktWs && CapB::L.wstotal >= kKktWs && CapC::L.wstotal >= kKktWs &&
-                  CapD::L.wstotal >= kKktWs && CapA32::L.wstotal >= kKktWs && CapC32::L.wstotal >= kKktWs &&
-                  CapE::L.wstotal >= kKktWs,
+static_assert(fits_every_class(kKktWs),
               "a solver class's workspace is smaller than one wavefront's of the KKT kernel");
 static_assert(std::is_same<CapEv::RT, double>::value && !CapEv::deep && !CapEv::eq,
               "the KKT kernel runs the fp64 factorisation of the global-row class");
 
-// LDS carve-up (doubles)
-constexpr int K_PP = 0;                       // p, internal layout (<= 64)
-constexpr int K_OB = K_PP + 64;               // obstacle x (16), y (16)
-constexpr int K_RV = K_OB + 2 * NMPC_MAX_OBS; // Solver::rvars; [30], [31] = cost weights
-constexpr int K_ST = K_RV + 32;               // phase-timer slots (NMPC_STAMPS builds write them)
-constexpr int K_X = K_ST + PH_COUNT;          // trajectory, 8 per stage
-constexpr int K_TRIG = K_X + 8 * NS;
-constexpr int K_INC = K_TRIG + 8 * NS;        // prefix / suffix sum scratch; the sweeps' P / p buffers
-constexpr int K_LAM = K_INC + 8 * NS;
-constexpr int K_DX = K_LAM + 8 * NS;          // the right-hand side's state step
+// LDS carve-up (doubles): the unit's head (its prefix-sum scratch also holds the sweeps' P / p
+// buffers), then
+constexpr int K_DX = B_END;                   // the right-hand side's state step
 constexpr int K_QS = K_DX + 8 * NS;           // q_k (8), S_k[0][3], S_k[0][4] per stage
 constexpr int K_SW = K_QS + 10 * NS;          // S~ (48), R~ (22), r~ (8) of the current stage
 constexpr int K_FIX = K_SW + 48 + 22 + 8;     // fixed-control masks, one int per stage
 constexpr int K_TOTAL = K_FIX + NS / 2 + 2;
 static_assert(8 * NS >= 144, "the sweeps' P / p buffers live in the prefix-sum scratch");
 static_assert(K_TOTAL * 8 <= 32 * 1024, "KKT kernel LDS");
-
-// nmpc_point.hip's (later in this unit): the scenario load and the stage summary that this kernel
-// shares with the kernels at a solve's point
-__device__ __forceinline__ void point_load(Solver<CapEv>& S, const Params* __restrict__ prm, int lane,
-                                           const double* pb, const double* xb);
-__device__ __forceinline__ void point_summary(Solver<CapEv>& S, int k, double obj_factor, const double* sg,
-                                              const double* yb, double delta, double c03, double c04);
 
 __global__ __launch_bounds__(WAVE) void nmpc_kkt_kernel(const Params* __restrict__ prm, int B, KktIO io) {
   __shared__ __attribute__((aligned(16))) double smem[K_TOTAL];
@@ -76,22 +61,18 @@ __global__ __launch_bounds__(WAVE) void nmpc_kkt_kernel(const Params* __restrict
   Solver<CapEv> S{};
   LDS double* sm = (LDS double*)smem;
   GLB double* gw = (GLB double*)(io.ws + (long long)b * kKktWs);
-  S.P = (const CST Params*)prm; S.sm = sm; S.lane_ = threadIdx.x; S.b = b;
-  S.N = prm->N; S.m = prm->m; S.nobs = prm->nobs; S.nw = prm->nw; S.ng = prm->ng; S.T = prm->T;
-  S.nb = prm->nb; S.nuE = prm->nuE; S.nwE = prm->nwE;
-  S.U = gw + kKktU; S.gl = gw + kKktGl; S.Hl = gw + kKktHl; S.tc = gw + kKktTc; S.dc = gw + kKktDc;
+  bind_solver(S, prm, sm, gw, b, kKktU, kKktGl, kKktHl, kKktTc, kKktDc);
   S.Qs = gw + kKktQs; S.K = gw + kKktK; S.Rk = gw + kKktRk; S.kf = gw + kKktKf;
   GLB double* Rd = gw + kKktRd;  // sigma_x, the kernel's layout
   GLB double* rv = gw + kKktRv;  // the right-hand side's control terms
   GLB double* dU = gw + kKktDu;  // its step
-  S.pp = sm + K_PP; S.obx = sm + K_OB; S.oby = S.obx + NMPC_MAX_OBS; S.rvars = sm + K_RV; S.stamps = sm + K_ST;
-  S.X = sm + K_X; S.trig = sm + K_TRIG; S.inc = sm + K_INC; S.lam = sm + K_LAM; S.qs = sm + K_QS;
+  S.qs = sm + K_QS;
   S.Pa = S.inc; S.Pb = S.inc + 64; S.pva = S.inc + 128; S.pvb = S.inc + 136;
   S.St = sm + K_SW; S.Rc = S.St + 48; S.Rv = S.Rc + 22;
   S.fixm = (LDS int*)(sm + K_FIX);
   LDS double* dX = sm + K_DX;
-  const int N = S.N, m = S.m, nb = S.nb, nw = S.nw, ng = S.ng, nwE = S.nwE, nuE = S.nuE;
-  const int nxE = prm->nxE, nXE = nxE * (N + 1);
+  const int N = S.N, m = S.m, nw = S.nw, ng = S.ng, nwE = S.nwE, nuE = S.nuE;
+  const int nXE = prm->nxE * (N + 1);
   const int lane = S.lanef();
   const double* yb = io.lam_g ? io.lam_g + (long long)b * io.ld_lam_g : nullptr;
   const double* xb = io.x + (long long)b * io.ld_x;
@@ -115,7 +96,8 @@ __global__ __launch_bounds__(WAVE) void nmpc_kkt_kernel(const Params* __restrict
   };
 
   // ---------------- scenario data
-  point_load(S, prm, lane, io.p + (long long)b * io.ld_p, xb);
+  load_params(S, prm, lane, io.p + (long long)b * io.ld_p);
+  load_controls(S, prm, lane, xb, true);
 
   // ---------------- the weights: sigma_x (lane k: its stage's controls, +inf = fixed), sigma_s
   bool bad = !(delta >= 0.0) || delta == INFINITY;
@@ -145,9 +127,7 @@ __global__ __launch_bounds__(WAVE) void nmpc_kkt_kernel(const Params* __restrict
   sync();
 
   // ---------------- rollout, stage costs (their transcendentals), derivatives, multipliers
-  S.rollout(S.U, S.X);
-  if (lane < N) (void)S.stage_cost(S.X + lane * 8, S.tc + lane * 12);
-  sync();
+  point_rollout(S, lane);
   S.derivs<true, true>(S.X, S.U, S.tc);
   if (yb) S.adjoint(io.obj_factor, yb);
   else S.adjoint(io.obj_factor, (const double*)nullptr);
@@ -173,33 +153,8 @@ __global__ __launch_bounds__(WAVE) void nmpc_kkt_kernel(const Params* __restrict
       rv[i] = (rwb && e >= 0) ? -rwb[(long long)d * nwE + e] : 0.0;
     }
     if (k >= 1 && k <= N) {
-      const LDS double* xk = S.X + k * 8;
-      double q8[8];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) q8[c] = 0.0;
-      if (rgb) {
-        const double* rg = rgb + (long long)d * ng;
-        double qx = 0.0, qy = 0.0;
-        for (int i = 0; i < m; ++i) {
-          const double t = -rg[k * m + i];
-          if (i < nb) {
-            const int bi = boxidx(i);
-#pragma unroll
-            for (int c = 2; c < 8; ++c) q8[c] = c == bi ? t : q8[c];
-          } else {
-            const int o = i - nb;
-            const double ddx = xk[0] - S.obx[o], ddy = xk[1] - S.oby[o];
-            const double idd = rsq(ddx * ddx + ddy * ddy);
-            qx += t * (-(ddx * idd));
-            qy += t * (-(ddy * idd));
-          }
-        }
-        q8[0] = qx;
-        q8[1] = qy;
-      }
-      LDS double* qo = S.qs + k * 10;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) qo[c] = q8[c];
+      const double* rg = rgb ? rgb + (long long)d * ng : nullptr;
+      point_stage_q(S, k, rg != nullptr, [&](int i) { return -rg[k * m + i]; });
     }
     sync();
     // 7. the solves
@@ -214,17 +169,8 @@ __global__ __launch_bounds__(WAVE) void nmpc_kkt_kernel(const Params* __restrict
         o[e] = S.fixed(i) ? 0.0 : dU[i];
       }
     }
-    if (io.jdw) {
-      double* o = io.jdw + ((long long)b * io.nr + d) * ng;
-      for (int r = lane; r < ng; r += WAVE) o[r] = r < m ? 0.0 : S.row_jd(r, dX);
-    }
-    if (io.dX) {
-      double* o = io.dX + ((long long)b * io.nr + d) * nXE;
-      for (int i = lane; i < prm->nX; i += WAVE) {
-        const int kk = i >> 3, c = i & 7;
-        if (c < nxE) o[kk * nxE + c] = dX[i];
-      }
-    }
+    if (io.jdw) put_rows_jd(S, lane, dX, io.jdw + ((long long)b * io.nr + d) * ng);
+    if (io.dX) put_trajectory(prm, lane, dX, io.dX + ((long long)b * io.nr + d) * nXE);
     sync();
   }
 }

@@ -2,11 +2,16 @@
 // the fused reverse-mode sensitivity (nmpc_solve_adjoint.hip), the fused forward-mode
 // sensitivity (nmpc_solve_tangent.hip) and the feedback policy (nmpc_solve_policy.hip).  Each of
 // them is the sequence
-//   point_bind, point_load, point_rollout, point_weights (info = -11), point_derivs,
-//   [its own second-order data], point_ladder (info = 1), point_verdict, point_unit_grads,
+//   point_bind, load_params, load_controls, point_rollout, point_weights (info = -11),
+//   point_derivs, [its own second-order data], point_ladder (info = 1), point_verdict,
+//   point_unit_grads,
 // then its own per-seed or per-direction work; the tangent and policy kernels also share
-// point_curvature, point_reads and point_direction_rhs.  point_load and point_summary serve
-// nmpc_kkt_kernel too (declared there: that file comes earlier in the unit).
+// point_curvature, point_reads and point_direction_rhs.  The LDS head, bind_solver, the scenario
+// load, point_rollout, point_dyn2, point_summary and point_reads are nmpc_eval_shared.hip's, shared
+// with the kernels at given points; point_unit_grads, point_curvature and point_direction_rhs keep
+// their own text for the unit-weight gradients, the obstacle curvature, the tangent and q_k: on
+// the shared helpers the three kernels' instructions changed and two of them measured slower
+// (DESIGN.md 26).
 //
 // Part of the evaluation kernel's translation unit (nmpc_eval.hip includes this file after
 // nmpc_adjoint.hip and before nmpc_solve_adjoint.hip), so everything is the text the solver
@@ -20,9 +25,7 @@
 
 namespace {
 
-static_assert(CapA::L.wstotal >= kPointWs && CapB::L.wstotal >= kPointWs && CapC::L.wstotal >= kPointWs &&
-                  CapD::L.wstotal >= kPointWs && CapA32::L.wstotal >= kPointWs && CapC32::L.wstotal >= kPointWs &&
-                  CapE::L.wstotal >= kPointWs,
+static_assert(fits_every_class(kPointWs),
               "a solver class's workspace is smaller than one wavefront's of a solution-point kernel");
 static_assert(kPointXi + 8 * kEvalStages <= kKktK, "the unit-weight gradients and xi live in the stage summaries' slice");
 
@@ -31,16 +34,7 @@ static_assert(kPointXi + 8 * kEvalStages <= kKktK, "the unit-weight gradients an
 // stage's entries into registers before the pullback's sweep uses the scratch again, and the
 // next seed's sweeps find it dead.  23.6 KB: six workgroups per CU's 160 KiB, where the KKT
 // kernel's 27.7 KB allow five
-constexpr int A_PP = 0;                       // p, internal layout (<= 64)
-constexpr int A_OB = A_PP + 64;               // obstacle x (16), y (16)
-constexpr int A_RV = A_OB + 2 * NMPC_MAX_OBS; // Solver::rvars; [30], [31] = cost weights
-constexpr int A_ST = A_RV + 32;               // phase-timer slots (NMPC_STAMPS builds write them)
-constexpr int A_X = A_ST + PH_COUNT;          // trajectory, 8 per stage
-constexpr int A_TRIG = A_X + 8 * NS;
-constexpr int A_INC = A_TRIG + 8 * NS;        // prefix / suffix sum scratch; the sweeps' P / p buffers; the
-                                              // seed's state step (dX/dw) q between forward and pullback
-constexpr int A_LAM = A_INC + 8 * NS;         // lam, then each seed's nu or each direction's xi
-constexpr int A_QS = A_LAM + 8 * NS;          // q_k (8), S_k[0][3], S_k[0][4] per stage
+constexpr int A_QS = B_END;                   // q_k (8), S_k[0][3], S_k[0][4] per stage
 constexpr int A_SW = A_QS + 10 * NS;          // S~ (48), R~ (22), r~ (8) of the current stage
 constexpr int A_FIX = A_SW + 48 + 22 + 8;     // fixed-control masks, one int per stage
 constexpr int A_TOTAL = A_FIX + NS / 2 + 2;
@@ -82,13 +76,9 @@ struct PointRefs {
 __device__ __forceinline__ PointRefs point_bind(Solver<CapEv>& S, const Params* __restrict__ prm, LDS double* sm,
                                                 const PointIO& io, int b) {
   GLB double* gw = (GLB double*)(io.ws + (long long)b * kPointWs);
-  S.P = (const CST Params*)prm; S.sm = sm; S.lane_ = threadIdx.x; S.b = b;
-  S.N = prm->N; S.m = prm->m; S.nobs = prm->nobs; S.nw = prm->nw; S.ng = prm->ng; S.T = prm->T;
-  S.nb = prm->nb; S.nuE = prm->nuE; S.nwE = prm->nwE;
-  S.U = gw + kKktU; S.gl = gw + kKktGl; S.Hl = gw + kKktHl; S.tc = gw + kKktTc; S.dc = gw + kKktDc;
+  bind_solver(S, prm, sm, gw, b, kKktU, kKktGl, kKktHl, kKktTc, kKktDc);
   S.Qs = gw + kKktQs; S.K = gw + kKktK; S.Rk = gw + kKktRk; S.kf = gw + kKktKf;
-  S.pp = sm + A_PP; S.obx = sm + A_OB; S.oby = S.obx + NMPC_MAX_OBS; S.rvars = sm + A_RV; S.stamps = sm + A_ST;
-  S.X = sm + A_X; S.trig = sm + A_TRIG; S.inc = sm + A_INC; S.lam = sm + A_LAM; S.qs = sm + A_QS;
+  S.qs = sm + A_QS;
   S.Pa = S.inc; S.Pb = S.inc + 64; S.pva = S.inc + 128; S.pvb = S.inc + 136;
   S.St = sm + A_SW; S.Rc = S.St + 48; S.Rv = S.Rc + 22;
   S.fixm = (LDS int*)(sm + A_FIX);
@@ -105,40 +95,6 @@ __device__ __forceinline__ PointRefs point_bind(Solver<CapEv>& S, const Params* 
   R.Rd = gw + kKktRd; R.rv = gw + kKktRv; R.dU = gw + kKktDu;
   R.sg = gw + kPointSg; R.yv = gw + kPointY; R.uw = gw + kPointUw; R.xw = gw + kPointXi;
   return R;
-}
-
-// scenario data: p (the scenario's row pb), obstacle centres and cost weights to LDS, the
-// controls of xb to the workspace in the kernel's 6-per-stage layout, unit row scaling.  The
-// caller's sync() follows
-__device__ __forceinline__ void point_load(Solver<CapEv>& S, const Params* __restrict__ prm, int lane,
-                                           const double* pb, const double* xb) {
-  if (lane < PH_COUNT) S.stamps[lane] = 0.0;
-  for (int i = lane; i < prm->np; i += WAVE) {
-    const int e = ext_p(prm, i);
-    S.pp[i] = e >= 0 ? pb[e] : 0.0;
-  }
-  sync();
-  if (lane < NMPC_MAX_OBS) {
-    const bool on = lane < S.nobs;
-    S.obx[lane] = on ? (prm->oxp[lane] >= 0 ? S.pp[prm->oxp[lane]] : prm->ox[lane]) : 0.0;
-    S.oby[lane] = on ? (prm->oyp[lane] >= 0 ? S.pp[prm->oyp[lane]] : prm->oy[lane]) : 0.0;
-  }
-  if (lane == 0) {
-    S.rvars[30] = prm->w1p >= 0 ? S.pp[prm->w1p] : prm->w1;
-    S.rvars[31] = prm->w2p >= 0 ? S.pp[prm->w2p] : prm->w2;
-  }
-  for (int i = lane; i < S.nw; i += WAVE) {
-    const int e = ext_u(prm, i);
-    S.U[i] = e >= 0 ? xb[e] : 0.0;
-  }
-  for (int r = lane; r < S.ng; r += WAVE) S.dc[r] = 1.0;  // unscaled rows
-}
-
-// rollout and stage costs (their transcendentals)
-__device__ __forceinline__ void point_rollout(Solver<CapEv>& S, int lane) {
-  S.rollout(S.U, S.X);
-  if (lane < S.N) (void)S.stage_cost(S.X + lane * 8, S.tc + lane * 12);
-  sync();
 }
 
 // the barrier weights, Solver.barrier_weights' operations in their order:
@@ -191,90 +147,6 @@ __device__ __forceinline__ bool point_weights(Solver<CapEv>& S, const Params* __
 __device__ __forceinline__ void point_derivs(Solver<CapEv>& S, const PointRefs& R) {
   S.derivs<true, true>(S.X, S.U, S.tc);
   S.adjoint(1.0, R.yb);
-}
-
-// second derivatives of lam_{k+1}^T T f(x_k, u_k) before the factor T, stage k < N on lane k:
-// the three entries of d2_xx and S_k's two.  Two uses, two roundings: a stage summary adds
-// T * e into Q (a fused multiply-add), point_curvature assigns T * e (a rounded product)
-struct Dyn2 { double e33, e44, e34, e03, e04; };
-__device__ __forceinline__ Dyn2 point_dyn2(const Solver<CapEv>& S, int k) {
-  const LDS double* tg = S.trig + k * 8;
-  const double ct = tg[0], stt = tg[1], cp = tg[2], sp = tg[3], v = tg[4];
-  const LDS double* ln = S.lam + (k + 1) * 8;
-  const double l0 = ln[0], l1 = ln[1], l2 = ln[2];
-  Dyn2 e;
-  e.e33 = -l0 * v * cp * ct - l1 * v * sp * ct - l2 * v * stt;
-  e.e44 = -l0 * v * cp * ct - l1 * v * sp * ct;
-  e.e34 = l0 * v * sp * stt - l1 * v * cp * stt;
-  e.e03 = -l0 * cp * stt - l1 * sp * stt + l2 * ct;
-  e.e04 = -l0 * sp * ct + l1 * cp * ct;
-  return e;
-}
-
-// lane k <= N: the stage summary Q_k = obj_factor Hl_k + G_k^T (sigma_s + delta) G_k
-// + sum_o lam_{k,o} Hg_o + the dynamics terms of lam_{k+1}^T T f, and S_k's two entries -- the
-// expressions of Solver::assemble's Newton mode with D = sigma_s + delta, for k >= 1 (stage 0 is
-// constant in w: Q_0 = 0); the linear terms zero.  sg and yb may be null (weights, multipliers
-// of 0).  c03, c04: stage 0's S_0 where it enters too, so that the stored K_0 is the stage's gain
-// (the policy kernel's; 0.0 elsewhere)
-__device__ __forceinline__ void point_summary(Solver<CapEv>& S, int k, double obj_factor, const double* sg,
-                                              const double* yb, double delta, double c03, double c04) {
-  const int N = S.N, m = S.m, nb = S.nb;
-  const double T = S.T;
-  if (k > N) return;
-  double Q[36];
-#pragma unroll
-  for (int t = 0; t < 36; ++t) Q[t] = 0.0;
-  double s03 = 0.0, s04 = 0.0;
-  if (k >= 1) {  // the stages whose state depends on w
-    const LDS double* xk = S.X + k * 8;
-    double Qxy0 = 0, Qxy1 = 0, Qxy2 = 0;
-    double Qb[5] = {0, 0, 0, 0, 0};
-    for (int i = 0; i < m; ++i) {
-      const int r = k * m + i;
-      const double w = (sg ? sg[r] : 0.0) + delta;
-      if (i < nb) {
-        Qb[i] = w;
-      } else {
-        const double C = yb ? yb[r] : 0.0;
-        const int o = i - nb;
-        const double ddx = xk[0] - S.obx[o], ddy = xk[1] - S.oby[o];
-        const double idd = rsq(ddx * ddx + ddy * ddy);
-        const double gx = -(ddx * idd), gy = -(ddy * idd);
-        const double id3 = idd * idd * idd;
-        Qxy0 += w * gx * gx + C * (-ddy * ddy * id3);
-        Qxy1 += w * gx * gy + C * (ddx * ddy * id3);
-        Qxy2 += w * gy * gy + C * (-ddx * ddx * id3);
-      }
-    }
-    const int sv[6] = {0, 1, 2, 5, 6, 7};  // the states a stage cost reads
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-#pragma unroll
-      for (int bq = a; bq < 6; ++bq) Q[S.pk8(sv[a], sv[bq])] += obj_factor * S.Hl[k * 21 + hp(a, bq)];
-    }
-    Q[S.pk8(0, 0)] += Qxy0; Q[S.pk8(0, 1)] += Qxy1; Q[S.pk8(1, 1)] += Qxy2;
-    Q[S.pk8(2, 2)] += Qb[0]; Q[S.pk8(3, 3)] += Qb[1]; Q[S.pk8(5, 5)] += Qb[2];
-    Q[S.pk8(6, 6)] += Qb[3]; Q[S.pk8(7, 7)] += Qb[4];
-    if (k < N) {
-      const Dyn2 e = point_dyn2(S, k);
-      Q[S.pk8(3, 3)] += T * e.e33;
-      Q[S.pk8(4, 4)] += T * e.e44;
-      Q[S.pk8(3, 4)] += T * e.e34;
-      s03 = T * e.e03;
-      s04 = T * e.e04;
-    }
-  } else {
-    s03 = c03;
-    s04 = c04;
-  }
-#pragma unroll
-  for (int t = 0; t < 36; ++t) S.Qs[k * 36 + t] = Q[t];
-  LDS double* qo = S.qs + k * 10;
-#pragma unroll
-  for (int c = 0; c < 8; ++c) qo[c] = 0.0;
-  qo[8] = s03;
-  qo[9] = s04;
 }
 
 // the delta ladder: delta = 0, the stage summaries with D = sigma_s + delta, Solver::riccati; on
@@ -390,17 +262,6 @@ __device__ __forceinline__ PointCurv point_curvature(Solver<CapEv>& S, const Poi
     c.s04 = T * e.e04;
   }
   return c;
-}
-
-// which entries of a direction something reads (lane i: internal entry i), and the entry's
-// place pe in the caller's layout
-__device__ __forceinline__ bool point_reads(const Solver<CapEv>& S, const Params* __restrict__ prm, int lane, int& pe) {
-  bool reads = lane < 10;
-  if (lane == prm->w1p || lane == prm->w2p) reads = true;
-  for (int o = 0; o < S.nobs; ++o)
-    if (lane == prm->oxp[o] || lane == prm->oyp[o]) reads = true;
-  pe = lane < prm->np ? ext_p(prm, lane) : -1;
-  return reads && pe >= 0;
 }
 
 // one direction dd of the parameters up to the sync() before Solver::resolve:

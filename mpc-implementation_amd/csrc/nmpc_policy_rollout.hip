@@ -80,21 +80,12 @@ __global__ __launch_bounds__(WAVE) void nmpc_policy_rollout_kernel(const Params*
   const long long sc = live ? s : M - 1;    // lanes past M recompute the last sample
   const long long col = (long long)b * M + sc;  // the sample's column of every output
 
-  // ---------------- scenario data (as the evaluation kernel loads it), and Xbar
-  for (int i = lane; i < prm->np; i += WAVE) {
-    const int e = ext_p(prm, i);
-    S.pp[i] = e >= 0 ? io.p[(long long)b * io.ld_p + e] : 0.0;
-  }
+  // ---------------- scenario data (the parameter half of nmpc_eval_shared.hip without the phase
+  // timers' slots, which this carve-up does not have), and Xbar
+  load_p(S, prm, lane, io.p + (long long)b * io.ld_p);
   sync();
-  if (lane < NMPC_MAX_OBS) {
-    const bool on = lane < S.nobs;
-    S.obx[lane] = on ? (prm->oxp[lane] >= 0 ? S.pp[prm->oxp[lane]] : prm->ox[lane]) : 0.0;
-    S.oby[lane] = on ? (prm->oyp[lane] >= 0 ? S.pp[prm->oyp[lane]] : prm->oy[lane]) : 0.0;
-  }
-  if (lane == 0) {
-    S.rvars[30] = prm->w1p >= 0 ? S.pp[prm->w1p] : prm->w1;
-    S.rvars[31] = prm->w2p >= 0 ? S.pp[prm->w2p] : prm->w2;
-  }
+  load_obstacles(S, prm, lane);
+  load_weights(S, prm, lane);
   {
     const double* Xb = io.Xbar + (long long)b * io.ld_Xbar;
     for (int i = lane; i < nXE; i += WAVE) {

@@ -111,16 +111,11 @@ __global__ __launch_bounds__(WAVE) void nmpc_policy_rollout_adjoint_kernel(const
   const long long sc = live ? s : M - 1;        // lanes past M recompute the last sample
   const long long col = (long long)b * M + sc;  // the sample's column of every per-sample output
 
-  // ---------------- scenario data (as the forward kernel loads it), and Xbar
-  for (int i = lane; i < prm->np; i += WAVE) {
-    const int e = ext_p(prm, i);
-    S.pp[i] = e >= 0 ? io.p[(long long)b * io.ld_p + e] : 0.0;
-  }
+  // ---------------- scenario data (as the forward kernel loads it, without the obstacle centres:
+  // no row is evaluated here), and Xbar
+  load_p(S, prm, lane, io.p + (long long)b * io.ld_p);
   sync();
-  if (lane == 0) {
-    S.rvars[30] = prm->w1p >= 0 ? S.pp[prm->w1p] : prm->w1;
-    S.rvars[31] = prm->w2p >= 0 ? S.pp[prm->w2p] : prm->w2;
-  }
+  load_weights(S, prm, lane);
   {
     const double* Xb = io.Xbar + (long long)b * io.ld_Xbar;
     for (int i = lane; i < nXE; i += WAVE) {

@@ -13,7 +13,10 @@
 // Execution model: the products kernel's.  One wavefront per (scenario, direction chunk),
 // stage k on lane k, rows and variables strided over the lanes, control flow wave-uniform.
 // Once per wavefront:
-//   1. scenario data, rollout and stage costs as nmpc_products_kernel;
+//   1. scenario data, rollout and stage costs.  This kernel takes the unit's LDS head and
+//      bind_solver from nmpc_eval_shared.hip and keeps its own text for everything else: each
+//      helper tried in its place changed the kernel's instructions, and the kernel with them
+//      measured slower;
 //   2. where a cost weight comes from p: the stage costs and their gradients with the weights
 //      (1, 0) and (0, 1) (stage_cost and derivs<false, true> on the swapped weights, as the
 //      solve's lam_p block forms the unit-weight costs), kept by lane k;
@@ -49,21 +52,12 @@
 
 namespace {
 
-static_assert(CapA::L.wstotal >= kPprodWs && CapB::L.wstotal >= kPprodWs && CapC::L.wstotal >= kPprodWs &&
-                  CapD::L.wstotal >= kPprodWs && CapA32::L.wstotal >= kPprodWs && CapC32::L.wstotal >= kPprodWs &&
-                  CapE::L.wstotal >= kPprodWs,
+static_assert(fits_every_class(kPprodWs),
               "a solver class's workspace is smaller than one wavefront's of the parameter-products kernel");
 
-// LDS carve-up (doubles)
-constexpr int Q_PP = 0;                       // p, internal layout (<= 64)
-constexpr int Q_OB = Q_PP + 64;               // obstacle x (16), y (16)
-constexpr int Q_RV = Q_OB + 2 * NMPC_MAX_OBS; // Solver::rvars; [30], [31] = cost weights
-constexpr int Q_ST = Q_RV + 32;               // phase-timer slots (NMPC_STAMPS builds write them)
-constexpr int Q_X = Q_ST + PH_COUNT;          // trajectory, 8 per stage
-constexpr int Q_TRIG = Q_X + 8 * NS;
-constexpr int Q_INC = Q_TRIG + 8 * NS;        // prefix / suffix sum scratch
-constexpr int Q_LAM = Q_INC + 8 * NS;         // lam, then each direction's mu
-constexpr int Q_DX = Q_LAM + 8 * NS;          // the direction's state tangent xi
+// LDS carve-up (doubles): the unit's head (its multipliers' buffer holds lam, then each
+// direction's mu), then
+constexpr int Q_DX = B_END;                   // the direction's state tangent xi
 constexpr int Q_CR = Q_DX + 8 * NS;           // the direction's Hxu_k^T xi_k
 constexpr int Q_DP = Q_CR + NS;               // the direction, internal p layout (<= 64)
 constexpr int Q_TOTAL = Q_DP + 64;
@@ -77,12 +71,7 @@ __global__ __launch_bounds__(WAVE) void nmpc_pproducts_kernel(const Params* __re
   Solver<CapEv> S{};
   LDS double* sm = (LDS double*)smem;
   GLB double* gw = (GLB double*)(io.ws + ((long long)b * chunks + chunk) * kPprodWs);
-  S.P = (const CST Params*)prm; S.sm = sm; S.lane_ = threadIdx.x; S.b = b;
-  S.N = prm->N; S.m = prm->m; S.nobs = prm->nobs; S.nw = prm->nw; S.ng = prm->ng; S.T = prm->T;
-  S.nb = prm->nb; S.nuE = prm->nuE; S.nwE = prm->nwE;
-  S.U = gw + kProdU; S.gl = gw + kProdGl; S.Hl = gw + kProdHl; S.tc = gw + kProdTc; S.dc = gw + kProdDc;
-  S.pp = sm + Q_PP; S.obx = sm + Q_OB; S.oby = S.obx + NMPC_MAX_OBS; S.rvars = sm + Q_RV; S.stamps = sm + Q_ST;
-  S.X = sm + Q_X; S.trig = sm + Q_TRIG; S.inc = sm + Q_INC; S.lam = sm + Q_LAM;
+  bind_solver(S, prm, sm, gw, b, kProdU, kProdGl, kProdHl, kProdTc, kProdDc);
   GLB double* oc = gw + kPprodOc;
   LDS double* dX = sm + Q_DX;
   // lane k's copy of xi_k[0:2] moved for one obstacle row: components 0 and 1 of its own row of
@@ -100,7 +89,7 @@ __global__ __launch_bounds__(WAVE) void nmpc_pproducts_kernel(const Params* __re
   const double* xb = io.x + (long long)b * io.ld_x;
   const double* db = io.dp ? io.dp + (long long)b * io.ld_dp : nullptr;
 
-  // ---------------- scenario data (as nmpc_products_kernel loads it)
+  // ---------------- scenario data (load_params' and load_controls' text)
   if (lane < PH_COUNT) S.stamps[lane] = 0.0;
   for (int i = lane; i < np; i += WAVE) {
     const int e = ext_p(prm, i);
@@ -179,7 +168,7 @@ __global__ __launch_bounds__(WAVE) void nmpc_pproducts_kernel(const Params* __re
 #pragma unroll
     for (int t = 0; t < 21; ++t) Hc[t] = sig * S.Hl[k * 21 + t];
   }
-  if (k <= N && yb) {  // y-weighted obstacle curvature: nmpc_products_kernel's, rows in order
+  if (k <= N && yb) {  // y-weighted obstacle curvature (obstacle_curvature's text), rows in order
     const LDS double* xk = S.X + k * 8;
     for (int o = 0; o < S.nobs; ++o) {
       const double C = yb[k * m + nb + o];
@@ -194,7 +183,7 @@ __global__ __launch_bounds__(WAVE) void nmpc_pproducts_kernel(const Params* __re
       }
     }
   }
-  if (k < N) {  // second derivatives of lam_{k+1}^T T f(x_k, u_k): Solver::assemble's dyn branch
+  if (k < N) {  // second derivatives of lam_{k+1}^T T f(x_k, u_k) (point_dyn2's text)
     const LDS double* tg = S.trig + k * 8;
     const double ct = tg[0], stt = tg[1], cp = tg[2], sp = tg[3], v = tg[4];
     const LDS double* ln = S.lam + (k + 1) * 8;

@@ -14,8 +14,9 @@
 // Execution model: the solver's.  One wavefront per (scenario, direction chunk), stage k on
 // lane k, rows and decision variables strided over the lanes, control flow wave-uniform.
 // Once per wavefront:
-//   1. scenario data, rollout and stage costs as nmpc_eval_kernel (the stage costs fill the
-//      transcendental cache that derivs<true, true> reads);
+//   1. scenario data, rollout and stage costs (load_params, load_controls, point_rollout of
+//      nmpc_eval_shared.hip: the stage costs fill the transcendental cache that
+//      derivs<true, true> reads);
 //   2. derivs<true, true>: gl, Hl; adjoint(obj_factor, lam_g): lam_{k+1};
 //   3. lane k keeps its stage's second-order data in registers for every direction:
 //      Hq = obj_factor Hl_k + sum_o lam_{k,o} Hg_o (21 packed entries over x, y, z, x5, x6, x7),
@@ -36,21 +37,12 @@
 
 namespace {
 
-static_assert(CapA::L.wstotal >= kProdWs && CapB::L.wstotal >= kProdWs && CapC::L.wstotal >= kProdWs &&
-                  CapD::L.wstotal >= kProdWs && CapA32::L.wstotal >= kProdWs && CapC32::L.wstotal >= kProdWs &&
-                  CapE::L.wstotal >= kProdWs,
+static_assert(fits_every_class(kProdWs),
               "a solver class's workspace is smaller than one wavefront's of the products kernel");
 
-// LDS carve-up (doubles)
-constexpr int P_PP = 0;                       // p, internal layout (<= 64)
-constexpr int P_OB = P_PP + 64;               // obstacle x (16), y (16)
-constexpr int P_RV = P_OB + 2 * NMPC_MAX_OBS; // Solver::rvars; [30], [31] = cost weights
-constexpr int P_ST = P_RV + 32;               // phase-timer slots (NMPC_STAMPS builds write them)
-constexpr int P_X = P_ST + PH_COUNT;          // trajectory, 8 per stage
-constexpr int P_TRIG = P_X + 8 * NS;
-constexpr int P_INC = P_TRIG + 8 * NS;        // prefix / suffix sum scratch
-constexpr int P_LAM = P_INC + 8 * NS;         // lam, then each direction's mu
-constexpr int P_DX = P_LAM + 8 * NS;          // the direction's tangent trajectory
+// LDS carve-up (doubles): the unit's head (its multipliers' buffer holds lam, then each
+// direction's mu), then
+constexpr int P_DX = B_END;                   // the direction's tangent trajectory
 constexpr int P_CR = P_DX + 8 * NS;           // the direction's Hxu_k^T dX_k
 constexpr int P_TOTAL = P_CR + NS;
 static_assert(P_TOTAL * 8 <= 32 * 1024, "products kernel LDS");
@@ -63,49 +55,21 @@ __global__ __launch_bounds__(WAVE) void nmpc_products_kernel(const Params* __res
   Solver<CapEv> S{};
   LDS double* sm = (LDS double*)smem;
   GLB double* gw = (GLB double*)(io.ws + ((long long)b * chunks + chunk) * kProdWs);
-  S.P = (const CST Params*)prm; S.sm = sm; S.lane_ = threadIdx.x; S.b = b;
-  S.N = prm->N; S.m = prm->m; S.nobs = prm->nobs; S.nw = prm->nw; S.ng = prm->ng; S.T = prm->T;
-  S.nb = prm->nb; S.nuE = prm->nuE; S.nwE = prm->nwE;
-  S.U = gw + kProdU; S.gl = gw + kProdGl; S.Hl = gw + kProdHl; S.tc = gw + kProdTc; S.dc = gw + kProdDc;
-  S.pp = sm + P_PP; S.obx = sm + P_OB; S.oby = S.obx + NMPC_MAX_OBS; S.rvars = sm + P_RV; S.stamps = sm + P_ST;
-  S.X = sm + P_X; S.trig = sm + P_TRIG; S.inc = sm + P_INC; S.lam = sm + P_LAM;
+  bind_solver(S, prm, sm, gw, b, kProdU, kProdGl, kProdHl, kProdTc, kProdDc);
   LDS double* dX = sm + P_DX;
   LDS double* cr = sm + P_CR;
-  const int N = S.N, m = S.m, nb = S.nb, nw = S.nw, ng = S.ng, nwE = S.nwE;
-  const int nxE = prm->nxE, nXE = nxE * (N + 1);
+  const int N = S.N, m = S.m, nb = S.nb, ng = S.ng, nwE = S.nwE;
+  const int nXE = prm->nxE * (N + 1);
   const double T = S.T;
   const int lane = S.lanef();
   const double* yb = io.lam_g ? io.lam_g + (long long)b * io.ld_lam_g : nullptr;
-  const double* xb = io.x + (long long)b * io.ld_x;
   const double* vb = io.v + (long long)b * io.ld_v;
 
-  // ---------------- scenario data (as nmpc_eval_kernel loads it)
-  if (lane < PH_COUNT) S.stamps[lane] = 0.0;
-  for (int i = lane; i < prm->np; i += WAVE) {
-    const int e = ext_p(prm, i);
-    S.pp[i] = e >= 0 ? io.p[(long long)b * io.ld_p + e] : 0.0;
-  }
+  // ---------------- scenario data, rollout, stage costs, derivatives, multipliers
+  load_params(S, prm, lane, io.p + (long long)b * io.ld_p);
+  load_controls(S, prm, lane, io.x + (long long)b * io.ld_x, true);
   sync();
-  if (lane < NMPC_MAX_OBS) {
-    const bool on = lane < S.nobs;
-    S.obx[lane] = on ? (prm->oxp[lane] >= 0 ? S.pp[prm->oxp[lane]] : prm->ox[lane]) : 0.0;
-    S.oby[lane] = on ? (prm->oyp[lane] >= 0 ? S.pp[prm->oyp[lane]] : prm->oy[lane]) : 0.0;
-  }
-  if (lane == 0) {
-    S.rvars[30] = prm->w1p >= 0 ? S.pp[prm->w1p] : prm->w1;
-    S.rvars[31] = prm->w2p >= 0 ? S.pp[prm->w2p] : prm->w2;
-  }
-  for (int i = lane; i < nw; i += WAVE) {
-    const int e = ext_u(prm, i);
-    S.U[i] = e >= 0 ? xb[e] : 0.0;
-  }
-  for (int r = lane; r < ng; r += WAVE) S.dc[r] = 1.0;  // unscaled rows
-  sync();
-
-  // ---------------- rollout, stage costs (their transcendentals), derivatives, multipliers
-  S.rollout(S.U, S.X);
-  if (lane < N) (void)S.stage_cost(S.X + lane * 8, S.tc + lane * 12);
-  sync();
+  point_rollout(S, lane);
   S.derivs<true, true>(S.X, S.U, S.tc);
   if (yb) S.adjoint(io.obj_factor, yb);
   else S.adjoint(io.obj_factor, (const double*)nullptr);
@@ -117,43 +81,30 @@ __global__ __launch_bounds__(WAVE) void nmpc_products_kernel(const Params* __res
 #pragma unroll
   for (int t = 0; t < 21; ++t) Hq[t] = 0.0;
   double d33 = 0.0, d34 = 0.0, d44 = 0.0, s03 = 0.0, s04 = 0.0;
-  double E03 = 0.0, E04 = 0.0, E13 = 0.0, E14 = 0.0, E23 = 0.0, b00 = 0.0, b10 = 0.0, b20 = 0.0;
-  if (k < N) S.stage_AB(k, E03, E04, E13, E14, E23, b00, b10, b20);
+  const StageAB ab = point_stage_ab(S, k);
   if (stage) {
 #pragma unroll
     for (int t = 0; t < 21; ++t) Hq[t] = io.obj_factor * S.Hl[k * 21 + t];
-    if (yb) {  // y-weighted obstacle curvature: Solver::assemble's, rows in order
-      const LDS double* xk = S.X + k * 8;
+    if (yb) {  // y-weighted obstacle curvature, rows in order; the sum is open to contraction
       double q00 = 0.0, q01 = 0.0, q11 = 0.0;
       for (int o = 0; o < S.nobs; ++o) {
-        const double C = yb[k * m + nb + o];
-        const double ddx = xk[0] - S.obx[o], ddy = xk[1] - S.oby[o];
-        const double idd = rsq(ddx * ddx + ddy * ddy);
-        const double id3 = idd * idd * idd;
-        q00 += C * (-ddy * ddy * id3);
-        q01 += C * (ddx * ddy * id3);
-        q11 += C * (-ddx * ddx * id3);
+        const ObsCurv h = obstacle_curvature(S, k, o, yb[k * m + nb + o]);
+        q00 += h.h00; q01 += h.h01; q11 += h.h11;
       }
       if (S.nobs > 0) { Hq[hp(0, 0)] += q00; Hq[hp(0, 1)] += q01; Hq[hp(1, 1)] += q11; }
     }
-    if (k < N) {  // second derivatives of lam_{k+1}^T T f(x_k, u_k): Solver::assemble's dyn branch
-      const LDS double* tg = S.trig + k * 8;
-      const double ct = tg[0], stt = tg[1], cp = tg[2], sp = tg[3], v = tg[4];
-      const LDS double* ln = S.lam + (k + 1) * 8;
-      const double l0 = ln[0], l1 = ln[1], l2 = ln[2];
-      d33 = T * (-l0 * v * cp * ct - l1 * v * sp * ct - l2 * v * stt);
-      d44 = T * (-l0 * v * cp * ct - l1 * v * sp * ct);
-      d34 = T * (l0 * v * sp * stt - l1 * v * cp * stt);
-      s03 = T * (-l0 * cp * stt - l1 * sp * stt + l2 * ct);
-      s04 = T * (-l0 * sp * ct + l1 * cp * ct);
+    if (k < N) {
+      const Dyn2 e = point_dyn2(S, k);
+      d33 = T * e.e33; d44 = T * e.e44; d34 = T * e.e34;
+      s03 = T * e.e03; s04 = T * e.e04;
     }
   }
   sync();  // lam is rewritten by every direction's sweep
 
   // ---------------- directions c, c + chunks, ...
   for (int d = chunk; d < io.nv; d += chunks) {
-    const double* vd = vb + (long long)d * nwE;
     // 4. tangent rollout
+    const double* vd = vb + (long long)d * nwE;
     double du[6];
 #pragma unroll
     for (int c = 0; c < 6; ++c) du[c] = (k < N && c < S.nuE) ? vd[k * S.nuE + c] : 0.0;
@@ -171,9 +122,9 @@ __global__ __launch_bounds__(WAVE) void nmpc_products_kernel(const Params* __res
         for (int c = 0; c < 5; ++c) dx[3 + c] = dx[3 + c] + S.inc[j * 8 + c];
       }
       if (k < N) {  // stage 0: dX_0 = 0, only B_0 du_0
-        S.inc[k * 8 + 5] = k == 0 ? b00 * du[0] : (E03 * dx[3] + E04 * dx[4]) + b00 * du[0];
-        S.inc[k * 8 + 6] = k == 0 ? b10 * du[0] : (E13 * dx[3] + E14 * dx[4]) + b10 * du[0];
-        S.inc[k * 8 + 7] = k == 0 ? b20 * du[0] : E23 * dx[3] + b20 * du[0];
+        S.inc[k * 8 + 5] = k == 0 ? ab.b00 * du[0] : (ab.E03 * dx[3] + ab.E04 * dx[4]) + ab.b00 * du[0];
+        S.inc[k * 8 + 6] = k == 0 ? ab.b10 * du[0] : (ab.E13 * dx[3] + ab.E14 * dx[4]) + ab.b10 * du[0];
+        S.inc[k * 8 + 7] = k == 0 ? ab.b20 * du[0] : ab.E23 * dx[3] + ab.b20 * du[0];
       }
     }
     sync();
@@ -210,32 +161,16 @@ __global__ __launch_bounds__(WAVE) void nmpc_products_kernel(const Params* __res
     }
     sync();
     // 5. J v and the tangent out
-    if (io.jv) {
-      double* o = io.jv + ((long long)b * io.nv + d) * ng;
-      for (int r = lane; r < ng; r += WAVE) o[r] = r < m ? 0.0 : S.row_jd(r, dX);
-    }
-    if (io.dX) {
-      double* o = io.dX + ((long long)b * io.nv + d) * nXE;
-      for (int i = lane; i < prm->nX; i += WAVE) {
-        const int kk = i >> 3, c = i & 7;
-        if (c < nxE) o[kk * nxE + c] = dX[i];
-      }
-    }
+    if (io.jv) put_rows_jd(S, lane, dX, io.jv + ((long long)b * io.nv + d) * ng);
+    if (io.dX) put_trajectory(prm, lane, dX, io.dX + ((long long)b * io.nv + d) * nXE);
     if (!io.hv) {
       sync();
       continue;
     }
     // 7. mu_k = h_k + A_k^T mu_{k+1}
     S.adjoint(1.0, (const double*)nullptr);
-    // 8. (W v)_{u_k}
-    double* o = io.hv + ((long long)b * io.nv + d) * nwE;
-    for (int i = lane; i < nw; i += WAVE) {
-      const int e = ext_u(prm, i);
-      if (e < 0) continue;
-      const int kk = i / 6;
-      const double g = S.grad_u(i);
-      o[e] = (i == 6 * kk && kk >= 1) ? g + cr[kk] : g;
-    }
+    // 8. (W v)_{u_k}: stage 0's cross term is absent
+    put_grad_u(S, prm, lane, cr, true, false, io.hv + ((long long)b * io.nv + d) * nwE);
     sync();
   }
 }

@@ -17,7 +17,7 @@
 // Execution model: the siblings'.  One wavefront per scenario, fp64, stage k on lane k, rows
 // and variables strided over the lanes, control flow wave-uniform.
 // Once per wavefront:
-//   1. point_load, point_rollout: scenario data, rollout and stage costs;
+//   1. load_params, load_controls, point_rollout: scenario data, rollout and stage costs;
 //   2. point_weights: the barrier weights; an equality row, lbx > ubx or a weight that is not a
 //      finite non-negative number ends the scenario with info = -11 and NaN outputs;
 //      point_derivs: gl, Hl, lam_{k+1};
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(WAVE) void nmpc_solve_adjoint_kernel(const Params* 
   LDS double* sm = (LDS double*)smem;
   const PointRefs R = point_bind(S, prm, sm, io.pt, b);
   GLB double *rv = R.rv, *dU = R.dU, *sg = R.sg, *yv = R.yv, *uw = R.uw;
-  LDS double* dX = sm + A_INC;
+  LDS double* dX = sm + B_INC;
   const int N = S.N, m = S.m, nb = S.nb, nw = S.nw, ng = S.ng, nwE = S.nwE;
   const int np = prm->np, npE = prm->npE, nxE = prm->nxE, nXE = nxE * (N + 1);
   const int w1p = prm->w1p, w2p = prm->w2p;
@@ -68,7 +68,8 @@ __global__ __launch_bounds__(WAVE) void nmpc_solve_adjoint_kernel(const Params* 
     point_verdict(S, io.pt, lane, verdict, delta);
   };
 
-  point_load(S, prm, lane, io.pt.p + (long long)b * io.pt.ld_p, R.xb);
+  load_params(S, prm, lane, io.pt.p + (long long)b * io.pt.ld_p);
+  load_controls(S, prm, lane, R.xb, true);
   sync();
   point_rollout(S, lane);
 
@@ -89,13 +90,9 @@ __global__ __launch_bounds__(WAVE) void nmpc_solve_adjoint_kernel(const Params* 
   double d33 = 0.0, d34 = 0.0, d44 = 0.0, s03 = 0.0, s04 = 0.0;  // (stage 0's s03, s04 are not in qs)
   if (io.pbar) {
     if (stage) {  // lam_g-weighted obstacle curvature: nmpc_adjoint_kernel's, rows in order
-      const LDS double* xk = S.X + k * 8;
       for (int o = 0; o < S.nobs; ++o) {
-        const double C = yb[k * m + nb + o];
-        const double ddx = xk[0] - S.obx[o], ddy = xk[1] - S.oby[o];
-        const double idd = rsq(ddx * ddx + ddy * ddy);
-        const double id3 = idd * idd * idd;
-        q00 += C * (-ddy * ddy * id3); q01 += C * (ddx * ddy * id3); q11 += C * (-ddx * ddx * id3);
+        const ObsCurv h = obstacle_curvature(S, k, o, yb[k * m + nb + o]);
+        q00 += h.h00; q01 += h.h01; q11 += h.h11;
       }
     }
     if (k < N) {

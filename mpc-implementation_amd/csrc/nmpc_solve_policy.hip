@@ -24,7 +24,7 @@
 // Execution model: the siblings'.  One wavefront per scenario, fp64, stage k on lane k, rows
 // and variables strided over the lanes, control flow wave-uniform.
 // Once per wavefront:
-//   1. point_load, point_rollout, point_weights (info = -11 and NaN outputs), point_derivs,
+//   1. load_params, load_controls, point_rollout, point_weights (info = -11 and NaN outputs), point_derivs,
 //      point_curvature, point_ladder with stage 0's cross term (info = 1 and NaN outputs);
 //   2. lane k writes K_k (compacted to nu x nx, a fixed control's row 0.0), A_k, B_k and X*_k;
 //      with directions and kff wanted, point_unit_grads.
@@ -63,7 +63,8 @@ __global__ __launch_bounds__(WAVE) void nmpc_solve_policy_kernel(const Params* _
     point_verdict(S, io.pt, lane, verdict, delta);
   };
 
-  point_load(S, prm, lane, io.pt.p + (long long)b * io.pt.ld_p, R.xb);
+  load_params(S, prm, lane, io.pt.p + (long long)b * io.pt.ld_p);
+  load_controls(S, prm, lane, R.xb, true);
   sync();
   point_rollout(S, lane);
   if (point_weights(S, prm, R, k)) {

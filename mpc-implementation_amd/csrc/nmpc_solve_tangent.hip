@@ -18,7 +18,7 @@
 // Execution model: the siblings'.  One wavefront per scenario, fp64, stage k on lane k, rows
 // and variables strided over the lanes, control flow wave-uniform.
 // Once per wavefront:
-//   1. to 4. point_load, point_rollout, point_weights (info = -11 and NaN outputs),
+//   1. to 4. load_params, load_controls, point_rollout, point_weights (info = -11 and NaN outputs),
 //      point_derivs, point_curvature (what every direction's h_k needs, in registers),
 //      point_ladder (info = 1 and NaN outputs), point_unit_grads.
 // Per direction (the factorisation is shared):
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(WAVE) void nmpc_solve_tangent_kernel(const Params* 
   LDS double* sm = (LDS double*)smem;
   const PointRefs R = point_bind(S, prm, sm, io.pt, b);
   GLB double *dU = R.dU, *sg = R.sg, *jpv = R.yv, *xw = R.xw;
-  LDS double* dX = sm + A_INC;   // (dX/dw) dx, from Solver::forward
+  LDS double* dX = sm + B_INC;   // (dX/dw) dx, from Solver::forward
   const int N = S.N, m = S.m, nw = S.nw, ng = S.ng, nwE = S.nwE;
   const int npE = prm->npE, nxE = prm->nxE, nXE = nxE * (N + 1);
   const int lane = S.lanef(), k = lane;
@@ -54,7 +54,8 @@ __global__ __launch_bounds__(WAVE) void nmpc_solve_tangent_kernel(const Params* 
     point_verdict(S, io.pt, lane, verdict, delta);
   };
 
-  point_load(S, prm, lane, io.pt.p + (long long)b * io.pt.ld_p, R.xb);
+  load_params(S, prm, lane, io.pt.p + (long long)b * io.pt.ld_p);
+  load_controls(S, prm, lane, R.xb, true);
   sync();
   point_rollout(S, lane);
   if (point_weights(S, prm, R, k)) {

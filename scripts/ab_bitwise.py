@@ -12,7 +12,9 @@ the solved cases of tests/solve_adjoint_ref.py (na = 3 seeds of all three kinds,
 directions), and on one batch per exit of the kernels -- fixed controls, info = -11, and info = 1
 with the ladder exhausted.  On the solved cases it also dumps evaluate, products, param_products,
 adjoint_products and policy_rollout (5 samples), each through the host entry point and through the
-device one, so every batched entry point is covered.  The points themselves are dumped too, so equal inputs are shown, and
+device one, so every batched entry point is covered, and the given-point kernels' other branches
+through the device entry points: lam_g absent, one output at a time, one seed kind at a time, the
+evaluation without the certificate and without any gradient.  The points themselves are dumped too, so equal inputs are shown, and
 --compare takes NaNs in the same places as equal whatever their payloads.
 """
 import os, sys
@@ -105,7 +107,39 @@ def fused(path):
         Kraw = t(np.swapaxes(pol["K"], -1, -2))  # the kernel's column-major blocks
         dev["roll"] = s.policy_rollout_device(dP, dx, t(pol["X"]), Kraw, t(e0), w=t(w), lbx=db[0], ubx=db[1],
                                               lbg=db[2], ubg=db[3], want=("J", "viol", "nsat", "X", "U"))
+        # the kernels' other branches, through the device entry points (an absent output or input is a
+        # null pointer there): lam_g absent; one output at a time; one seed kind at a time; the
+        # evaluation without the certificate and without any gradient
+        v3, dp3 = bm(sd["x_bar"]), bm(dp)
+        seeds = {"y": bm(sd["lam_g_bar"]), "z": v3, "Xbar": bm(sd["X_bar"])}
+        br = {"ev_noy": empty(f=(B,), g=(B, ng), X=(B, nX), grad_f=(B, nw), grad_l=(B, nw), kkt=(B, 5)),
+              "ev_nokkt": empty(f=(B,), g=(B, ng), X=(B, nX), grad_f=(B, nw), grad_l=(B, nw)),
+              "ev_nograd": empty(f=(B,), g=(B, ng), X=(B, nX)),
+              "prod_noy": empty(jv=(B, 3, ng), hv=(B, 3, nw), dX=(B, 3, nX)),
+              "prod_jv": empty(jv=(B, 3, ng)), "prod_hv": empty(hv=(B, 3, nw)),
+              "pprod_noy": empty(jp=(B, 3, ng), hp=(B, 3, nw), dXp=(B, 3, nX), gp=(B, npp)),
+              "pprod_gp": empty(gp=(B, npp)), "pprod_nohp": empty(jp=(B, 3, ng), dXp=(B, 3, nX), gp=(B, npp)),
+              "adjp_noy": empty(wbar=(B, 3, nw), pbar=(B, 3, npp)),
+              "adjp_wbar": empty(wbar=(B, 3, nw)), "adjp_pbar": empty(pbar=(B, 3, npp))}
+        s.evaluate_device(dx, dP, br["ev_noy"], lam_x=dlx, lbx=db[0], ubx=db[1], lbg=db[2], ubg=db[3])
+        s.evaluate_device(dx, dP, br["ev_nokkt"], lam_g=dlg, lam_x=dlx)
+        s.evaluate_device(dx, dP, br["ev_nograd"], lam_g=dlg)
+        s.products_device(dx, dP, v3, br["prod_noy"], obj_factor=0.7)
+        s.products_device(dx, dP, v3, br["prod_jv"], lam_g=dlg, obj_factor=0.7)
+        s.products_device(dx, dP, v3, br["prod_hv"], lam_g=dlg, obj_factor=0.7)
+        s.param_products_device(dx, dP, dp3, br["pprod_noy"], obj_factor=0.7)
+        s.param_products_device(dx, dP, None, br["pprod_gp"], lam_g=dlg, obj_factor=0.7)
+        s.param_products_device(dx, dP, dp3, br["pprod_nohp"], lam_g=dlg, obj_factor=0.7)
+        s.adjoint_products_device(dx, dP, br["adjp_noy"], obj_factor=0.7, **seeds)
+        s.adjoint_products_device(dx, dP, br["adjp_wbar"], lam_g=dlg, obj_factor=0.7, **seeds)
+        s.adjoint_products_device(dx, dP, br["adjp_pbar"], lam_g=dlg, obj_factor=0.7, **seeds)
+        for kind, seed in seeds.items():
+            br[f"adjp_{kind}"] = empty(wbar=(B, 3, nw), pbar=(B, 3, npp))
+            s.adjoint_products_device(dx, dP, br[f"adjp_{kind}"], lam_g=dlg, obj_factor=0.7, **{kind: seed})
         torch.cuda.synchronize()
+        for name in br:
+            for k, v in br[name].items():
+                out[f"{tag}_{name}_dev_{k}"] = v.cpu().numpy()
         for name in host:
             for k, v in host[name].items():
                 out[f"{tag}_{name}_{k}"] = np.asarray(v)
@@ -129,6 +163,12 @@ def fused(path):
                             sigma_s=ss, delta=dl)
             for k, v in r.items():
                 out[f"{name}_kkt{dl:g}_{k}"] = np.asarray(v)
+        # the KKT kernel's other branches: no row right-hand side, no multipliers
+        for tag, kw in (("norg", dict(r_w=sd["x_bar"], lam_g=sol["lam_g"])),
+                        ("noy", dict(r_w=sd["x_bar"], r_g=sd["lam_g_bar"]))):
+            r = s.kkt_solve(sol["x"], P.T, sigma_x=sx, sigma_s=ss, delta=1e-4, **kw)
+            for k, v in r.items():
+                out[f"{name}_kkt_{tag}_{k}"] = np.asarray(v)
         if name != "race_track_2":
             continue
         lbx, ubx, lbg, ubg = bounds

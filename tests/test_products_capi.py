@@ -48,7 +48,12 @@ def test_products_kernel_lives_in_the_evaluation_unit(tmp_path, monkeypatch):
     assert ge.source_hash() == before
     with open(copy / "nmpc_products.hip", "ab") as fh:
         fh.write(b"\n// x\n")
-    assert ge.source_hash() != before
+    moved = ge.source_hash()
+    assert moved != before
+    # and the file the unit's kernels share
+    with open(copy / "nmpc_eval_shared.hip", "ab") as fh:
+        fh.write(b"\n// x\n")
+    assert ge.source_hash() not in (before, moved)
 
 
 # the cases each mutant is shown on: ones where the mutated term exists (every case has
