@@ -783,6 +783,83 @@ int nmpc_policy_covariance_batch(nmpc_handle* h, int32_t B, int32_t nc,
                                  const double* obs_var, int64_t ld_obs_var,
                                  double* Sigma_out, double* sigma_u_out, double* sigma_g_out);
 
+/* The reverse sweep of that covariance, for a whole batch, in one launch: the gradient of a loss on
+ * the covariances and the back-offs with respect to everything the forward call reads -- the gains,
+ * the noise model, the plan and p -- so the chain solve -> policy -> covariance -> tighten -> next solve
+ * can be differentiated.  For each of B scenarios and each of nc cases, at the Sigma_k the forward call
+ * returned (Sigma_out; an input here, not recomputed), with seeds Sb_k on Sigma_k (k = 0 ... N), ub on
+ * the VARIANCES var_u = sigma_u^2 and gb on var_g = sigma_g^2 (the square root's chain rule is the
+ * caller's: var_bar = sigma_bar / (2 sigma)), the gradient of
+ *   L = sum_k <Sb_k, Sigma_k> + <ub, var_u> + <gb, var_g>
+ * by the recursion, with sym(S) = (S + S^T) / 2 and Lam symmetric throughout,
+ *   R_k(Lam): Lam[bi,bi] += gb[k,i]                      box row i on state bi
+ *             Lam[0:2,0:2] += gb[k,o] g g^T              obstacle row o, g as in the forward call
+ *             obs_var_bar[o] += gb[k,o]
+ *             pos = H_o (2 gb[k,o] Sigma_k[0:2,0:2] g)   H_o: the row's Hessian in (x, y) at Xbar_k
+ *             Xbar_bar[k,0:2] += pos;  p_bar[centre of o, where taken from p] -= pos
+ *   Lam_N = sym(Sb_N) + R_N
+ *   for k = N-1 ... 0:
+ *     M = Lam_{k+1} Acl_k,   G = 2 M Sigma_k
+ *     K_bar_k = B_k^T G + 2 diag(ub_k) K_k Sigma_k
+ *     (Xbar_bar_k, ubar_bar_k) += <G, dA_k> + <G K_k^T, dB_k> pulled back through the entries of A_k and
+ *                                 B_k, which depend on theta, psi (Xbar_k[3], [4]) and v (ubar_k[0]) alone
+ *     Lam_k = Acl_k^T M + sym(Sb_k) + K_k^T diag(ub_k) K_k + R_k
+ *   S0_bar = Lam_0,   W_bar = Lam_N + Lam_{N-1} + ... + Lam_1 (added in that order)
+ * Lam_k is the gradient with respect to a covariance injected at stage k: what a stage-varying W needs.
+ * With K NULL, Acl_k = A_k, var_u_bar contributes nothing and K_bar_out must be NULL.  Neither the clamp
+ * nor the bounds are inputs.
+ * Inputs (leading dimension: 0 shares one column across scenarios, else >= the vector length):
+ *   p, ubar, Xbar, K                  the forward call's, p, ubar and Xbar required
+ *   Sigma     (nx nx (N+1) nc x B)    required: the forward call's Sigma_out; only the lower triangle
+ *                                     (i >= j) of each block is read
+ *   Sigma_bar (nx nx (N+1) nc x B)    optional seed, Sigma's layout; any nx x nx blocks, symmetrised here
+ *   var_u_bar (nw nc x B)             optional seed, sigma_u_out's layout
+ *   var_g_bar (ng nc x B)             optional seed, sigma_g_out's layout
+ * At least one seed must be given.
+ * Outputs, each may be NULL, at least one must be given; case c of scenario b starts at (b nc + c) n,
+ * and a caller whose input is shared by the cases or the scenarios sums:
+ *   S0_bar_out      (nx nx x nc x B)        exactly symmetric: the G with dL = sum_ij G_ij dS_ij for
+ *                                           symmetric dS
+ *   W_bar_out       (nx nx x nc x B)        likewise
+ *   Lambda_out      (nx nx (N+1) x nc x B)  block k is Lam_k; block 0 equals S0_bar_out bitwise
+ *   obs_var_bar_out (n_obs x nc x B)
+ *   K_bar_out       (nu nx N x nc x B)      K_out's layout; needs K
+ *   ubar_bar_out    (nw x nc x B)
+ *   Xbar_bar_out    (nx(N+1) x nc x B)
+ *   p_bar_out       (np x nc x B)           exactly 0 outside the obstacle centres taken from p; obstacles
+ *                                           that name one entry are added in ascending order
+ * No floating-point atomics: two identical calls agree bitwise.  Cases are independent: a NaN in one
+ * case's Sigma or seeds stays in that case, a NaN K or plan of one scenario leaves its neighbours
+ * untouched.  All seeds 0 with finite inputs give exactly 0 everywhere.
+ * DEVICE pointers, enqueued on `stream`; never synchronises, allocates nothing and needs no
+ * workspace: the handle's memory is untouched.
+ * Return NMPC_E_INVALID before any device call, in this order: a NULL handle; B <= 0; nc <= 0 (or
+ * nc > 65535); a NULL p, ubar, Xbar or Sigma; every seed NULL; every output NULL; K_bar_out with a NULL
+ * K; obs_var_bar_out on a problem with n_obs = 0; a leading dimension that is neither 0 nor >= the
+ * vector length. */
+int nmpc_policy_covariance_adjoint_batch_dev(nmpc_handle* h, int32_t B, int32_t nc,
+                                             const double* p, int64_t ld_p, const double* ubar, int64_t ld_ubar,
+                                             const double* Xbar, int64_t ld_Xbar, const double* K, int64_t ld_K,
+                                             const double* Sigma, int64_t ld_Sigma,
+                                             const double* Sigma_bar, int64_t ld_Sigma_bar,
+                                             const double* var_u_bar, int64_t ld_var_u_bar,
+                                             const double* var_g_bar, int64_t ld_var_g_bar,
+                                             double* S0_bar_out, double* W_bar_out, double* Lambda_out,
+                                             double* obs_var_bar_out, double* K_bar_out, double* ubar_bar_out,
+                                             double* Xbar_bar_out, double* p_bar_out, void* stream);
+
+/* Same with HOST pointers; synchronous (staged through the handle's device buffer). */
+int nmpc_policy_covariance_adjoint_batch(nmpc_handle* h, int32_t B, int32_t nc,
+                                         const double* p, int64_t ld_p, const double* ubar, int64_t ld_ubar,
+                                         const double* Xbar, int64_t ld_Xbar, const double* K, int64_t ld_K,
+                                         const double* Sigma, int64_t ld_Sigma,
+                                         const double* Sigma_bar, int64_t ld_Sigma_bar,
+                                         const double* var_u_bar, int64_t ld_var_u_bar,
+                                         const double* var_g_bar, int64_t ld_var_g_bar,
+                                         double* S0_bar_out, double* W_bar_out, double* Lambda_out,
+                                         double* obs_var_bar_out, double* K_bar_out, double* ubar_bar_out,
+                                         double* Xbar_bar_out, double* p_bar_out);
+
 /* Optional per-iteration trace (debugging / parity): when enabled, the next
  * solve records NMPC_TRACE_FIELDS doubles per iteration per scenario into a
  * device buffer readable with nmpc_read_trace (host pointer,

@@ -214,7 +214,21 @@ struct CovIO {
   double *Sigma, *sigma_u, *sigma_g;
 };
 
+// DEVICE pointers, layouts and leading dimensions as nmpc_policy_covariance_adjoint_batch_dev
+// (include/nmpc_amd.h); p, ubar, Xbar and Sigma are required, one of the seeds Sigma_bar / var_u_bar /
+// var_g_bar and one of the eight outputs; K_bar only with K.  No workspace
+struct CovAdjIO {
+  const double *p, *ubar, *Xbar, *K, *Sigma, *Sigma_bar, *var_u_bar, *var_g_bar;
+  long long ld_p, ld_ubar, ld_Xbar, ld_K, ld_Sigma, ld_Sigma_bar, ld_var_u_bar, ld_var_g_bar;
+  double *S0_bar, *W_bar, *Lambda, *obs_var_bar, *K_bar, *ubar_bar, *Xbar_bar, *p_bar;
+};
+
 }  // namespace nmpc_impl
+
+// Enqueues the reverse sweep of the closed-loop covariances of B scenarios x nc cases on `stream`:
+// B x nc wavefronts laid out as nmpc_policy_covariance_launch's.  Same contract as nmpc_eval_launch.
+int nmpc_policy_covariance_adjoint_launch(const nmpc_impl::Params* dprm, int B, int nc,
+                                          const nmpc_impl::CovAdjIO& io, void* stream);
 
 // Enqueues the closed-loop covariances of B scenarios x nc cases on `stream`: B x nc wavefronts,
 // one per (scenario, case), lane = entry of the 8 x 8 matrix.  Same contract as nmpc_eval_launch.

@@ -242,3 +242,7 @@ int nmpc_policy_covariance_launch(const Params* dprm, int B, int nc, const CovIO
   hipLaunchKernelGGL(nmpc_policy_covariance_kernel, dim3(B, nc), dim3(WAVE), 0, (hipStream_t)stream, dprm, B, nc, io);
   return (int)hipGetLastError();
 }
+
+// the reverse sweep of that covariance, one wavefront per (scenario, case) again: a twelfth kernel
+// of this unit
+#include "nmpc_policy_covariance_adjoint.hip"

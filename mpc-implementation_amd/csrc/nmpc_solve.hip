@@ -5735,7 +5735,7 @@ int nmpc_solve_batch(nmpc_handle* h, int32_t B, const double* x0, int64_t ld_x0,
 }
 
 // ---- the batched entry points at given points.  One argument block, one check, one enqueue and
-// one staging routine serve the eleven entry-point pairs (X_batch on host pointers, X_batch_dev on
+// one staging routine serve the twelve entry-point pairs (X_batch on host pointers, X_batch_dev on
 // device pointers); a pair adds its own rules, its table of lengths and its launch callback
 struct CallArgs {
   // the inputs in the C argument order (absent ones null) and their leading dimensions
@@ -5743,7 +5743,7 @@ struct CallArgs {
   int64_t ld[12];
   int nin;
   // the double outputs in the C argument order
-  double* out[6];
+  double* out[8];
   int nout;
   // the optional int32 output (info, nsat) and its per-scenario length
   int32_t* iout;
@@ -5752,7 +5752,7 @@ struct CallArgs {
   double obj_factor;
   // filled by check: the vector length each input's leading dimension must cover, and the
   // per-scenario length of each double output
-  size_t vlen[12], olen[6];
+  size_t vlen[12], olen[8];
 };
 // fills the kernel's IO block from checked arguments (DEVICE pointers) and launches
 typedef int (*Launch)(const nmpc_handle* h, int32_t B, const CallArgs& a, void* stream);
@@ -6429,6 +6429,73 @@ int nmpc_policy_covariance_batch(nmpc_handle* h, int32_t B, int32_t nc, const do
              {Sigma_out, sigma_u_out, sigma_g_out}, 3, nullptr, 0, nc};
   if (int rc = cov_check(h, B, a)) return rc;
   return staged(h, B, a, cov_launch, "policy covariance", 0);
+}
+
+// ---- the reverse sweep of that covariance (kernel: nmpc_policy_covariance_adjoint.hip): inputs p,
+// ubar, Xbar, K, Sigma and the seeds Sigma_bar, var_u_bar, var_g_bar; outputs S0_bar, W_bar, Lambda,
+// obs_var_bar, K_bar, ubar_bar, Xbar_bar, p_bar of the nc cases
+static int covadj_check(const nmpc_handle* h, int32_t B, CallArgs& a) {
+  const char* count = nullptr;
+  if (a.n <= 0) count = "nc <= 0";
+  else if (a.n > 65535) count = "nc > 65535";
+  const char* own = nullptr;
+  if (all_null(a.in + 5, 3)) own = "every seed pointer is null (Sigma_bar, var_u_bar, var_g_bar)";
+  else if (all_null(a.out, 8))
+    own = "S0_bar_out, W_bar_out, Lambda_out, obs_var_bar_out, K_bar_out, ubar_bar_out, Xbar_bar_out and p_bar_out "
+          "are all null";
+  else if (!a.in[3] && a.out[4]) own = "K_bar_out needs K";
+  else if (h && a.out[3] && h->hp.nobs == 0) own = "obs_var_bar_out asked for on a problem without obstacles";
+  return check(h, B, count, a, 0x17, "required pointer is null (p, ubar, Xbar, Sigma)", own,
+               [](const Params& P, CallArgs& a) {
+                 const size_t nw = P.nwE, nx = P.nxE, nu = P.nuE, N = P.N, nc = a.n;
+                 set_lens(a.vlen, {(size_t)P.npE, nw, nx * (N + 1), nu * nx * N, nx * nx * (N + 1) * nc,
+                                   nx * nx * (N + 1) * nc, nw * nc, (size_t)P.ng * nc});
+                 set_lens(a.olen, {nx * nx * nc, nx * nx * nc, nx * nx * (N + 1) * nc, (size_t)P.nobs * nc,
+                                   nu * nx * N * nc, nw * nc, nx * (N + 1) * nc, (size_t)P.npE * nc});
+               });
+}
+static int covadj_launch(const nmpc_handle* h, int32_t B, const CallArgs& a, void* stream) {
+  CovAdjIO io;
+  io.p = a.in[0]; io.ubar = a.in[1]; io.Xbar = a.in[2]; io.K = a.in[3]; io.Sigma = a.in[4]; io.Sigma_bar = a.in[5];
+  io.var_u_bar = a.in[6]; io.var_g_bar = a.in[7];
+  io.ld_p = a.ld[0]; io.ld_ubar = a.ld[1]; io.ld_Xbar = a.ld[2]; io.ld_K = a.ld[3]; io.ld_Sigma = a.ld[4];
+  io.ld_Sigma_bar = a.ld[5]; io.ld_var_u_bar = a.ld[6]; io.ld_var_g_bar = a.ld[7];
+  io.S0_bar = a.out[0]; io.W_bar = a.out[1]; io.Lambda = a.out[2]; io.obs_var_bar = a.out[3]; io.K_bar = a.out[4];
+  io.ubar_bar = a.out[5]; io.Xbar_bar = a.out[6]; io.p_bar = a.out[7];
+  return nmpc_policy_covariance_adjoint_launch(h->dprm, (int)B, (int)a.n, io, stream);
+}
+
+int nmpc_policy_covariance_adjoint_batch_dev(nmpc_handle* h, int32_t B, int32_t nc, const double* p, int64_t ld_p,
+                                             const double* ubar, int64_t ld_ubar, const double* Xbar,
+                                             int64_t ld_Xbar, const double* K, int64_t ld_K, const double* Sigma,
+                                             int64_t ld_Sigma, const double* Sigma_bar, int64_t ld_Sigma_bar,
+                                             const double* var_u_bar, int64_t ld_var_u_bar, const double* var_g_bar,
+                                             int64_t ld_var_g_bar, double* S0_bar_out, double* W_bar_out,
+                                             double* Lambda_out, double* obs_var_bar_out, double* K_bar_out,
+                                             double* ubar_bar_out, double* Xbar_bar_out, double* p_bar_out,
+                                             void* stream) {
+  CallArgs a{{p, ubar, Xbar, K, Sigma, Sigma_bar, var_u_bar, var_g_bar},
+             {ld_p, ld_ubar, ld_Xbar, ld_K, ld_Sigma, ld_Sigma_bar, ld_var_u_bar, ld_var_g_bar}, 8,
+             {S0_bar_out, W_bar_out, Lambda_out, obs_var_bar_out, K_bar_out, ubar_bar_out, Xbar_bar_out, p_bar_out}, 8,
+             nullptr, 0, nc};
+  if (int rc = covadj_check(h, B, a)) return rc;
+  return enqueue(h, B, a, stream, covadj_launch, "policy covariance adjoint", 0);
+}
+
+int nmpc_policy_covariance_adjoint_batch(nmpc_handle* h, int32_t B, int32_t nc, const double* p, int64_t ld_p,
+                                         const double* ubar, int64_t ld_ubar, const double* Xbar, int64_t ld_Xbar,
+                                         const double* K, int64_t ld_K, const double* Sigma, int64_t ld_Sigma,
+                                         const double* Sigma_bar, int64_t ld_Sigma_bar, const double* var_u_bar,
+                                         int64_t ld_var_u_bar, const double* var_g_bar, int64_t ld_var_g_bar,
+                                         double* S0_bar_out, double* W_bar_out, double* Lambda_out,
+                                         double* obs_var_bar_out, double* K_bar_out, double* ubar_bar_out,
+                                         double* Xbar_bar_out, double* p_bar_out) {
+  CallArgs a{{p, ubar, Xbar, K, Sigma, Sigma_bar, var_u_bar, var_g_bar},
+             {ld_p, ld_ubar, ld_Xbar, ld_K, ld_Sigma, ld_Sigma_bar, ld_var_u_bar, ld_var_g_bar}, 8,
+             {S0_bar_out, W_bar_out, Lambda_out, obs_var_bar_out, K_bar_out, ubar_bar_out, Xbar_bar_out, p_bar_out}, 8,
+             nullptr, 0, nc};
+  if (int rc = covadj_check(h, B, a)) return rc;
+  return staged(h, B, a, covadj_launch, "policy covariance adjoint", 0);
 }
 
 int nmpc_shift_dev(nmpc_handle* h, int32_t B, double* p, int64_t ld_p, const double* u_sol, double* w_out,

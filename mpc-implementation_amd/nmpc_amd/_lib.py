@@ -36,6 +36,7 @@ EXPORTS = (
     "nmpc_policy_rollout_batch", "nmpc_policy_rollout_batch_dev",
     "nmpc_policy_rollout_adjoint_batch", "nmpc_policy_rollout_adjoint_batch_dev",
     "nmpc_policy_covariance_batch", "nmpc_policy_covariance_batch_dev",
+    "nmpc_policy_covariance_adjoint_batch", "nmpc_policy_covariance_adjoint_batch_dev",
 )
 
 _OPT_INT = ("max_iter", "acceptable_iter", "max_soc", "max_soft_resto_iters",
@@ -147,6 +148,10 @@ def lib():
     if hasattr(L, "nmpc_policy_covariance_batch") or not os.environ.get("NMPC_LIB"):
         L.nmpc_policy_covariance_batch.argtypes = [vp, C.c_int32, C.c_int32] + [dp, i64] * 7 + [dp] * 3
         L.nmpc_policy_covariance_batch_dev.argtypes = [vp, C.c_int32, C.c_int32] + [vp, i64] * 7 + [vp] * 3 + [vp]
+    if hasattr(L, "nmpc_policy_covariance_adjoint_batch") or not os.environ.get("NMPC_LIB"):
+        L.nmpc_policy_covariance_adjoint_batch.argtypes = [vp, C.c_int32, C.c_int32] + [dp, i64] * 8 + [dp] * 8
+        L.nmpc_policy_covariance_adjoint_batch_dev.argtypes = ([vp, C.c_int32, C.c_int32] + [vp, i64] * 8 + [vp] * 8
+                                                               + [vp])
     L.nmpc_set_trace.argtypes = [vp, C.c_int32]
     L.nmpc_read_trace.argtypes = [vp, C.c_int32, dp]
     L.nmpc_shift_dev.argtypes = [vp, C.c_int32, vp, i64, vp, vp, vp, vp, vp]

@@ -164,6 +164,86 @@ def policy_rollout(solver, p, ubar, Xbar, K, e0, w=None, lbx=None, ubx=None):
     return _rollout_function().apply(solver, p, ubar, Xbar, K, e0, w, lbx, ubx)
 
 
+@functools.lru_cache(maxsize=None)
+def _covariance_function():
+    import torch
+
+    from . import policy
+
+    def fold(G):  # the forward reads the entries i >= j of a column-major block: [..., j, i] with i >= j
+        return torch.triu(G + G.transpose(-1, -2), 1) + torch.diag_embed(torch.diagonal(G, dim1=-2, dim2=-1))
+
+    class _Covariance(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, solver, p, ubar, Xbar, K, S0, W, obs_var):
+            det = [None if t is None else t.detach().contiguous() for t in (p, ubar, Xbar, K, S0, W, obs_var)]
+            pd, ud, Xd, Kd, Sd, Wd, od = det
+            _, nu, nx = solver._policy_dims()
+            ctx.k_view = Kd is not None and tuple(Kd.shape[-2:]) == (nu, nx)
+            if ctx.k_view:  # policy_device's view (…, nu, nx): to the kernel's column-major blocks
+                Kd = Kd.transpose(-1, -2).contiguous()
+            r = solver.policy_covariance_device(pd, ud, Xd, Kd, Sd, W=Wd, obs_var=od, want=("Sigma", "sigma_u", "sigma_g"))
+            ctx.set_materialize_grads(False)  # an output the loss does not read seeds nothing
+            ctx.solver, ctx.ins, ctx.res = solver, (pd, ud, Xd, Kd, Sd, Wd, od), r
+            return r["Sigma"], r["sigma_u"], r["sigma_g"]
+
+        @staticmethod
+        def backward(ctx, Sb, sub, sgb):
+            s = ctx.solver
+            pd, ud, Xd, Kd, Sd, Wd, od = ctx.ins
+            if Kd is None:
+                sub = None  # sigma_u is identically 0 in the open loop
+            if Sb is None and sub is None and sgb is None:
+                return (None,) * 8
+            need = ctx.needs_input_grad  # (solver, p, ubar, Xbar, K, S0, W, obs_var)
+            names = ((1, "p_bar"), (2, "ubar_bar"), (3, "Xbar_bar"), (4, "K_bar"), (5, "S0_bar"), (6, "W_bar"),
+                     (7, "obs_var_bar"))
+            want = tuple(n for i, n in names if need[i] and ctx.ins[i - 1] is not None)
+            if not want:
+                return (None,) * 8
+            r = ctx.res
+            f64 = lambda t: None if t is None else t.detach().to(torch.float64).contiguous()  # noqa: E731
+            vu = None if sub is None else policy.var_seed(r["sigma_u"], f64(sub)).contiguous()
+            vg = None if sgb is None else policy.var_seed(r["sigma_g"], f64(sgb)).contiguous()
+            o = s.policy_covariance_adjoint_device(pd, ud, Xd, Kd, r["Sigma"], Sigma_bar=f64(Sb), var_u_bar=vu,
+                                                   var_g_bar=vg, want=want)
+            B = r["Sigma"].shape[0]
+
+            def grad(n, like, per_case=False):
+                """Output n summed over the cases (unless the input has them) and, for an input the
+                batch shares, over the scenarios."""
+                g = o.get(n)
+                if g is None:
+                    return None
+                if n == "K_bar" and ctx.k_view:
+                    g = g.transpose(-1, -2)
+                if n in ("S0_bar", "W_bar"):
+                    g = fold(g)
+                if not per_case:
+                    g = g.sum(1)
+                return g.sum(0) if like.dim() == g.dim() - 1 else g
+
+            return (None, grad("p_bar", pd), grad("ubar_bar", ud), grad("Xbar_bar", Xd),
+                    None if Kd is None else grad("K_bar", Kd), grad("S0_bar", Sd, True),
+                    None if Wd is None else grad("W_bar", Wd, True), None if od is None else grad("obs_var_bar", od))
+
+    return _Covariance
+
+
+def policy_covariance(solver, p, ubar, Xbar, K, S0, W=None, obs_var=None):
+    """The closed-loop covariance of the policy (:meth:`Solver.policy_covariance_device`, whose shapes
+    the arguments have; CUDA float64 tensors) as a differentiable function: returns ``Sigma``
+    (B,nc,N+1,nx,nx), ``sigma_u`` (B,nc,N,nu) and ``sigma_g`` (B,nc,N+1,m), through which ``backward``
+    reaches ``p``, ``ubar``, ``Xbar``, ``K``, ``S0``, ``W`` and ``obs_var`` -- each only if it requires
+    grad -- by one :meth:`Solver.policy_covariance_adjoint_device` launch; the square roots' chain rule
+    is :func:`nmpc_amd.policy.var_seed` (a deviation that is exactly 0 passes no gradient).  The
+    forward reads only the entries i >= j of ``S0`` and ``W``, so their gradients are folded onto those
+    entries: an off-diagonal one gets G_ij + G_ji, the diagonal G_ii and the unread triangle 0 --
+    perturbing one stored entry gives what autograd reports.  An input shared by the cases or by the
+    batch gets the sum.  Neither pass copies to the host or synchronises."""
+    return _covariance_function().apply(solver, p, ubar, Xbar, K, S0, W, obs_var)
+
+
 def solve(solver, p, lbx, ubx, lbg, ubg, x0=None, backward="host"):
     """Solves the batch at the parameters ``p`` -- a (B, np) float64 CUDA tensor that may require
     grad -- and returns the solution ``x`` (B, nw) and its state trajectory ``X`` (B, nx(N+1)) as

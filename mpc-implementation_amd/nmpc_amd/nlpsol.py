@@ -1312,6 +1312,128 @@ class Solver:
         _lib.check(_lib.lib().nmpc_policy_covariance_batch(self._h, B, nc, *_flat_ins(arrs), *ptr))
         return res
 
+    # ---- the reverse sweep of that covariance (nmpc_policy_covariance_adjoint_batch)
+    COVARIANCE_ADJ_OUT = ("S0_bar", "W_bar", "Lambda", "obs_var_bar", "K_bar", "ubar_bar", "Xbar_bar", "p_bar")
+
+    def _covariance_adjoint_shapes(self, B, nc):
+        N, nu, nx = self._policy_dims()
+        return {"S0_bar": (B, nc, nx, nx), "W_bar": (B, nc, nx, nx), "Lambda": (B, nc, N + 1, nx, nx),
+                "obs_var_bar": (B, nc, self.spec.n_obs), "K_bar": (B, nc, N, nx, nu), "ubar_bar": (B, nc, self.nw),
+                "Xbar_bar": (B, nc, N + 1, nx), "p_bar": (B, nc, self.np)}
+
+    def policy_covariance_adjoint_device(self, p, ubar, Xbar, K, Sigma, Sigma_bar=None, var_u_bar=None,
+                                         var_g_bar=None, out: dict | None = None,
+                                         want=("S0_bar", "K_bar", "ubar_bar", "Xbar_bar", "p_bar"), stream=None):
+        """The reverse sweep of :meth:`policy_covariance_device` at its ``Sigma`` (B,nc,N+1,nx,nx)
+        (``nmpc_policy_covariance_adjoint_batch_dev``, whose comment states the recursion): the
+        gradient of sum_k <Sigma_bar_k, Sigma_k> + <var_u_bar, sigma_u^2> + <var_g_bar, sigma_g^2> per
+        (scenario, case), torch CUDA float64 tensors in and out.  ``p``, ``ubar``, ``Xbar`` and ``K`` are
+        the forward call's (``K`` also in :meth:`policy_device`'s (…,nu,nx) view).  The seeds
+        ``Sigma_bar`` (B,nc,N+1,nx,nx) -- any blocks, symmetrised by the kernel --, ``var_u_bar``
+        (B,nc,N,nu) and ``var_g_bar`` (B,nc,N+1,m) are on the VARIANCES, may each be None or shared
+        (without the B), and one at least is required.  Returns a dict with the outputs named in
+        ``want`` and those preallocated in ``out``, each per (scenario, case): ``S0_bar`` and ``W_bar``
+        (B,nc,nx,nx), exactly symmetric; ``Lambda`` (B,nc,N+1,nx,nx), the gradient with respect to a
+        covariance injected at each stage; ``obs_var_bar`` (B,nc,n_obs); ``K_bar`` (B,nc,N,nx,nu), the
+        kernel's column-major blocks (needs ``K``); ``ubar_bar`` (B,nc,nw); ``Xbar_bar`` (B,nc,N+1,nx);
+        ``p_bar`` (B,nc,np), 0 outside the obstacle centres taken from p.  A caller whose input is
+        shared by the cases or the scenarios sums.  Enqueued on ``stream`` (default = current); never
+        synchronises the host, reads nothing back and uses no workspace of the handle."""
+        import torch  # plumbing only: device memory and streams
+
+        N, nu, nx = self._policy_dims()
+        m = self.ng // (N + 1)
+        if p is None or ubar is None or Xbar is None or Sigma is None:
+            raise ValueError("p, ubar, Xbar and Sigma are required")
+        assert Sigma.dim() in (4, 5) and tuple(Sigma.shape[-3:]) == (N + 1, nx, nx), ("Sigma", tuple(Sigma.shape))
+        nc = Sigma.shape[-4]
+        B = None
+        for t, lead in ((Sigma, 5), (p, 2), (ubar, 2), (Xbar, 3), (Sigma_bar, 5), (var_u_bar, 4), (var_g_bar, 4)):
+            if t is not None and t.dim() == lead:
+                B = t.shape[0]
+                break
+        if B is None:
+            raise ValueError("policy_covariance_adjoint_device: no argument carries the batch size")
+        if Sigma_bar is None and var_u_bar is None and var_g_bar is None:
+            raise ValueError("policy_covariance_adjoint_device: one of the seeds Sigma_bar, var_u_bar, var_g_bar "
+                             "is required")
+        if K is not None and tuple(K.shape[-2:]) == (nu, nx):
+            K = K.transpose(-1, -2)  # policy_device's view back to the kernel's column-major blocks
+        ins = _dev_ins((("p", p, (self.np,)), ("ubar", ubar, (self.nw,)), ("Xbar", Xbar, (N + 1, nx)),
+                        ("K", K, (N, nx, nu)), ("Sigma", Sigma, (nc, N + 1, nx, nx)),
+                        ("Sigma_bar", Sigma_bar, (nc, N + 1, nx, nx)), ("var_u_bar", var_u_bar, (nc, N, nu)),
+                        ("var_g_bar", var_g_bar, (nc, N + 1, m))), B)
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        shapes = self._covariance_adjoint_shapes(B, nc)
+        res = dict(out or {})
+        with torch.cuda.stream(stream):
+            for k in want:
+                if res.get(k) is None:
+                    res[k] = torch.empty(shapes[k], dtype=torch.float64, device=Sigma.device)
+        if all(res.get(k) is None for k in self.COVARIANCE_ADJ_OUT):
+            raise ValueError("policy_covariance_adjoint_device: one of " + ", ".join(self.COVARIANCE_ADJ_OUT)
+                             + " is required")
+        if K is None and res.get("K_bar") is not None:
+            raise ValueError("policy_covariance_adjoint_device: K_bar needs K")
+        ptr = _dev_outs(res, [(k, shapes[k]) for k in self.COVARIANCE_ADJ_OUT])
+        _lib.check(_lib.lib().nmpc_policy_covariance_adjoint_batch_dev(self._h, B, nc, *ins, *ptr, _stream_ptr(stream)))
+        return {k: v for k, v in res.items() if v is not None}
+
+    def policy_covariance_adjoint(self, p, ubar, Xbar, K, Sigma, Sigma_bar=None, var_u_bar=None, var_g_bar=None,
+                                  want=COVARIANCE_ADJ_OUT):
+        """:meth:`policy_covariance_adjoint_device` through the host entry point
+        (``nmpc_policy_covariance_adjoint_batch``), NumPy arrays in the same scenario-major shapes;
+        ``K`` (B,N,nu,nx) in row-major blocks, as :meth:`policy_fused` returns them, or None, and
+        ``K_bar`` (B,nc,N,nu,nx) likewise.  Each input may be shared (without the B).  Returns the
+        outputs named in ``want`` (``K_bar`` is left out when K is None, ``obs_var_bar`` when the
+        problem has no obstacles)."""
+        N, nu, nx = self._policy_dims()
+        m = self.ng // (N + 1)
+        if Sigma is None:
+            raise ValueError("Sigma is required")
+        Sigma = np.ascontiguousarray(Sigma, dtype=np.float64)
+        if Sigma.ndim not in (4, 5) or Sigma.shape[-3:] != (N + 1, nx, nx):
+            raise ValueError(f"Sigma: expected (nc,{N + 1},{nx},{nx}) or (B,nc,{N + 1},{nx},{nx}), got shape {Sigma.shape}")
+        nc = Sigma.shape[-4]
+        if K is not None:
+            K = np.asarray(K, dtype=np.float64)
+            if K.shape[-2:] != (nu, nx):
+                raise ValueError(f"K: expected blocks of ({nu},{nx}), got shape {K.shape}")
+            K = np.swapaxes(K, -1, -2)  # to the kernel's column-major blocks
+        fields = (("p", p, (self.np,)), ("ubar", ubar, (self.nw,)), ("Xbar", Xbar, (N + 1, nx)), ("K", K, (N, nx, nu)),
+                  ("Sigma", Sigma, (nc, N + 1, nx, nx)), ("Sigma_bar", Sigma_bar, (nc, N + 1, nx, nx)),
+                  ("var_u_bar", var_u_bar, (nc, N, nu)), ("var_g_bar", var_g_bar, (nc, N + 1, m)))
+        arrs, B = [], None
+        for name, a, tail in fields:
+            if a is None:
+                if name in ("p", "ubar", "Xbar"):
+                    raise ValueError(f"{name} is required")
+                arrs.append((None, 0))
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape == tail:
+                arrs.append((a, 0))
+                continue
+            if a.shape[1:] != tail or B not in (None, a.shape[0]):
+                raise ValueError(f"{name}: expected {tail} or (B,) + {tail}, got shape {a.shape}")
+            B = a.shape[0]
+            arrs.append((a, int(np.prod(tail))))
+        if B is None:
+            raise ValueError("policy_covariance_adjoint: no argument carries the batch size")
+        if Sigma_bar is None and var_u_bar is None and var_g_bar is None:
+            raise ValueError("policy_covariance_adjoint: one of the seeds Sigma_bar, var_u_bar, var_g_bar is required")
+        shapes = self._covariance_adjoint_shapes(B, nc)
+        res = {k: np.empty(shapes[k]) for k in self.COVARIANCE_ADJ_OUT
+               if k in want and not (K is None and k == "K_bar") and not (self.spec.n_obs == 0 and k == "obs_var_bar")}
+        if not res:
+            raise ValueError("policy_covariance_adjoint: one of " + ", ".join(self.COVARIANCE_ADJ_OUT) + " is required")
+        ptr = [_dptr(res[k]) if k in res else None for k in self.COVARIANCE_ADJ_OUT]
+        _lib.check(_lib.lib().nmpc_policy_covariance_adjoint_batch(self._h, B, nc, *_flat_ins(arrs), *ptr))
+        if "K_bar" in res:
+            res["K_bar"] = np.ascontiguousarray(np.swapaxes(res["K_bar"], -1, -2))
+        return res
+
     def shift_device(self, p, u_sol, w_out, v_t, w_t, stream=None):
         """Closed-loop shift on device (Python/NMPC_TT.py:13-30), see nmpc_shift_dev."""
         import torch

@@ -9,7 +9,8 @@ with torch ops on the caller's stream: nothing is copied to the host.  :func:`ro
 policy, clamped, on the nonlinear plant for many disturbance samples per scenario in one launch
 (``Solver.policy_rollout_device``): what it costs and whether it keeps the rows.  :func:`covariance`
 gives what those rollouts estimate in closed form, the state covariance around the plan and the
-standard deviation of every row and control (``Solver.policy_covariance_device``), and
+standard deviation of every row and control (``Solver.policy_covariance_device``),
+:func:`covariance_grad` its reverse sweep (``Solver.policy_covariance_adjoint_device``), and
 :func:`tighten` moves the bounds of the next solve inwards by a multiple of them."""
 from __future__ import annotations
 
@@ -137,6 +138,58 @@ def covariance(solver, pol: dict, sol: dict, p, S0, W=None, obs_var=None, c=None
     raw = pol["raw"]
     return solver.policy_covariance_device(p, ubar.contiguous(), raw["X"], raw["K"] if feedback else None, S0, W=W,
                                            obs_var=obs_var, out=out, want=want, stream=stream)
+
+
+def var_seed(sigma, sigma_b):
+    """The seed on a variance for the seed ``sigma_b`` on its standard deviation sigma = sqrt(max(var, 0)):
+    sigma_b / (2 sigma) where sigma > 0, 0 where sigma == 0 (the maximum's flat side), NaN where sigma is
+    NaN.  Torch ops only."""
+    import torch
+
+    safe = torch.where(sigma > 0, sigma, torch.ones_like(sigma))
+    return torch.where(sigma > 0, sigma_b / (2.0 * safe), torch.where(sigma != sigma, sigma, torch.zeros_like(sigma)))
+
+
+def covariance_grad(solver, pol: dict, sol: dict, p, cov: dict, Sigma_b=None, sigma_u_b=None, sigma_g_b=None, c=None,
+                    feedback: bool = True, out: dict | None = None,
+                    want=("S0_bar", "K_bar", "ubar_bar", "Xbar_bar", "p_bar"), stream=None):
+    """The gradient of a loss on :func:`covariance`'s result, in one launch
+    (``Solver.policy_covariance_adjoint_device``): ``cov`` is the dict :func:`covariance` returned for
+    the same ``pol``, ``sol``, ``p``, ``c`` and ``feedback`` and must hold ``Sigma``; the seeds
+    ``Sigma_b`` (B, nc, N+1, nx, nx), ``sigma_u_b`` (B, nc, N, nu) and ``sigma_g_b`` (B, nc, N+1, m) are on
+    Sigma and on the STANDARD DEVIATIONS (each may be None, one at least is given; ``cov`` must hold the
+    deviations that are seeded).  They are turned into seeds on the variances with :func:`var_seed`.
+    Returns the dict of ``Solver.policy_covariance_adjoint_device`` with the outputs asked for in
+    ``want`` or preallocated in ``out``, each per (scenario, case).  With ``c`` given,
+    ubar = u* + sum_d kff^(d) c_d, and the dict also holds ``c_bar`` (B, nc, nd) = <kff^(d), ubar_bar>
+    (``ubar_bar`` is then formed whether asked for or not).  With ``feedback=False`` the gains are not
+    read, ``sigma_u_b`` contributes nothing and ``K_bar`` is left out.  Nothing is copied to the host
+    and nothing synchronises."""
+    import torch
+
+    if cov.get("Sigma") is None:
+        raise ValueError("cov holds no Sigma: ask policy.covariance for it (want=(..., 'Sigma'))")
+    ubar = sol["x"]
+    kff = None
+    if c is not None:
+        kff = pol["kff"]
+        if kff is None:
+            raise ValueError("the policy holds no feedforward: it was formed without directions")
+        cc = c if c.dim() == 2 else c.unsqueeze(0).expand(kff.shape[0], -1)
+        ubar = ubar + torch.einsum("bdn,bd->bn", kff.reshape(kff.shape[0], kff.shape[1], -1), cc)
+        if "ubar_bar" not in want:
+            want = tuple(want) + ("ubar_bar",)
+    if not feedback:
+        want = tuple(k for k in want if k != "K_bar")
+    vu = None if (sigma_u_b is None or not feedback) else var_seed(cov["sigma_u"], sigma_u_b).contiguous()
+    vg = None if sigma_g_b is None else var_seed(cov["sigma_g"], sigma_g_b).contiguous()
+    raw = pol["raw"]
+    res = solver.policy_covariance_adjoint_device(p, ubar.contiguous(), raw["X"], raw["K"] if feedback else None,
+                                                  cov["Sigma"], Sigma_bar=Sigma_b, var_u_bar=vu, var_g_bar=vg, out=out,
+                                                  want=want, stream=stream)
+    if kff is not None:
+        res["c_bar"] = torch.einsum("bdn,bcn->bcd", kff.reshape(kff.shape[0], kff.shape[1], -1), res["ubar_bar"])
+    return res
 
 
 BOUND_INF = 1e19  # a bound at or beyond it is absent (IPOPT's nlp_lower / upper_bound_inf)
