@@ -860,6 +860,73 @@ int nmpc_policy_covariance_adjoint_batch(nmpc_handle* h, int32_t B, int32_t nc,
                                          double* obs_var_bar_out, double* K_bar_out, double* ubar_bar_out,
                                          double* Xbar_bar_out, double* p_bar_out);
 
+/* The cost-to-go expansion of that policy, for a whole batch, in one launch: the expected cost of the
+ * closed loop under an uncertain initial state and process noise, exact to second order -- the number
+ * the mean of the rollouts' sampled J estimates with O(1 / sqrt(M)) noise -- its variance to first
+ * order, and a local quadratic model of the cost-to-go at every stage.  For each of B scenarios, in
+ * fp64 and in the model's own dimensions (the no-gimbal model: nu = 3, nx = 5), at the GIVEN plan
+ * (Xbar_k, ubar_k), k = 0 ... N, and gains K_k:
+ *   the policy is u_k = ubar_k + K_k (x_k - Xbar_k), UNCLAMPED (K NULL: K_k = 0, open loop);
+ *   the plant is  x_{k+1} = x_k + T f(x_k, u_k) + w_k, started from x_0 + e0, e0 ~ (0, S0), w_k ~ (0, W);
+ *   the cost is   J = sum_{k < N} l_k(x_k; p), the stage cost as the rollouts sum it: it reads the state
+ *                 only, and stage N carries no cost.
+ * With V_k(x) the cost from stage k on without noise, lam_k = grad V_k and P_k = grad^2 V_k at Xbar_k:
+ *   lam_N = 0,  P_N = 0
+ *   for k = N-1 ... 0:
+ *     g_k, H_k = gradient and Hessian of l_k at Xbar_k
+ *     A_k, B_k = d x_{k+1} / d x_k, d x_{k+1} / d u_k at (Xbar_k, ubar_k);  Acl_k = A_k + B_k K_k, each
+ *                entry fl(A + fl(B K)) as nmpc_policy_covariance_batch_dev rounds it
+ *     Fxx, Fxu = second derivatives of lam_{k+1}^T T f at (Xbar_k, ubar_k): the dynamics' curvature
+ *                shifts the mean at the same order as the cost's (entries (theta, psi) x (theta, psi)
+ *                and (theta, psi) x speed only)
+ *     M_k   = H_k + Fxx + Fxu K_k + K_k^T Fxu^T       (the policy is affine: no further term)
+ *     lam_k = g_k + Acl_k^T lam_{k+1}
+ *     P_k   = M_k + Acl_k^T P_{k+1} Acl_k
+ *   J       = sum_k l_k(Xbar_k)
+ *   per case c, with <P, S> = sum_i P_ii S_ii + 2 sum_{i > j} P_ij S_ij:
+ *   dJ[c]   = 1/2 <P_0, S0[c]> + 1/2 <P_N + ... + P_1, W[c]>          E[J] = J + dJ to second order
+ *   varJ[c] = lam_0^T S0[c] lam_0 + sum_{k >= 1} lam_k^T W[c] lam_k   Var[J] to first order
+ * P_k may be indefinite: that is the model, and nothing is done about it.  W is the same at every
+ * stage, so its terms are summed over the stages before the cases.  The expansion is at the points
+ * given; it is the closed loop's own undisturbed trajectory -- and J + dJ the expected cost -- when Xbar
+ * is the plant's rollout of ubar from p's initial state, which X_out of nmpc_solve_policy_batch_dev
+ * with the solve's x_out is.  Neither the clamp, nor the rows, nor the bounds are inputs.
+ * Inputs: p, ubar, Xbar, K, S0 and W are nmpc_policy_covariance_batch_dev's, with its layouts and its
+ * leading-dimension rule (0 shares one column across scenarios, else >= the vector length); p, ubar and
+ * Xbar are required, K optional.  nc >= 0: with nc = 0 there are no cases and S0, W, dJ_out and varJ_out
+ * must be NULL; with nc > 0 S0 is required and W NULL means no process noise.  Only the lower triangle
+ * (i >= j) of each S0 and W block is read.
+ * Outputs, each may be NULL, at least one must be given:
+ *   J_out    (B)
+ *   lam_out  (nx(N+1) x B)       : X_out's layout; block N is exactly 0
+ *   P_out    (nx nx (N+1) x B)   : block k is P_k, column-major, exactly symmetric; block N is exactly 0
+ *   dJ_out   (nc x B)            varJ_out (nc x B)
+ * Cases are independent: a NaN in one case's S0 or W stays in that case's dJ and varJ.  A NaN K or Xbar
+ * (a policy with info != 0) makes that scenario's J, lam_0, P_0, dJ and varJ NaN beside bitwise-untouched
+ * neighbours (J is set to NaN where lam_0 holds one).  S0 = 0 with W NULL gives dJ = varJ = 0.  With
+ * N = 1, P_0 = H_0 exactly and K has no effect.  No floating-point atomics: two identical calls agree
+ * bitwise.
+ * DEVICE pointers, enqueued on `stream`; never synchronises.  Workspace: one slice of
+ * nmpc_products_batch_dev's per scenario (the controls, the stage costs' gradients and Hessians, the
+ * transcendental cache and the row scaling: 68 doubles for each of 64 stages, 34,816 bytes), taken from the handle's workspace, which is
+ * grown only when it does not cover B yet (a solve's workspace does); nothing else is allocated.
+ * Return NMPC_E_INVALID before any device call, in this order: a NULL handle; B <= 0; nc < 0; a NULL
+ * p, ubar or Xbar; a NULL S0 with nc > 0; S0, W, dJ_out or varJ_out given with nc = 0; every output
+ * NULL; a leading dimension that is neither 0 nor >= the vector length. */
+int nmpc_policy_value_batch_dev(nmpc_handle* h, int32_t B, int32_t nc,
+                                const double* p, int64_t ld_p, const double* ubar, int64_t ld_ubar,
+                                const double* Xbar, int64_t ld_Xbar, const double* K, int64_t ld_K,
+                                const double* S0, int64_t ld_S0, const double* W, int64_t ld_W,
+                                double* J_out, double* lam_out, double* P_out, double* dJ_out,
+                                double* varJ_out, void* stream);
+
+/* Same with HOST pointers; synchronous (staged through the handle's device buffer). */
+int nmpc_policy_value_batch(nmpc_handle* h, int32_t B, int32_t nc,
+                            const double* p, int64_t ld_p, const double* ubar, int64_t ld_ubar,
+                            const double* Xbar, int64_t ld_Xbar, const double* K, int64_t ld_K,
+                            const double* S0, int64_t ld_S0, const double* W, int64_t ld_W,
+                            double* J_out, double* lam_out, double* P_out, double* dJ_out, double* varJ_out);
+
 /* Optional per-iteration trace (debugging / parity): when enabled, the next
  * solve records NMPC_TRACE_FIELDS doubles per iteration per scenario into a
  * device buffer readable with nmpc_read_trace (host pointer,

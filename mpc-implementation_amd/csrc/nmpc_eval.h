@@ -223,7 +223,23 @@ struct CovAdjIO {
   double *S0_bar, *W_bar, *Lambda, *obs_var_bar, *K_bar, *ubar_bar, *Xbar_bar, *p_bar;
 };
 
+// DEVICE pointers, layouts and leading dimensions as nmpc_policy_value_batch_dev
+// (include/nmpc_amd.h); p, ubar and Xbar are required, S0 with nc > 0, and one of J / lam / P / dJ /
+// varJ (dJ and varJ only with nc > 0).  Workspace: one products-kernel slice per scenario
+// (Solver::derivs writes the stage costs' gradients and Hessians through global pointers)
+struct ValIO {
+  const double *p, *ubar, *Xbar, *K, *S0, *W;
+  long long ld_p, ld_ubar, ld_Xbar, ld_K, ld_S0, ld_W;
+  double *J, *lam, *P, *dJ, *varJ;
+  double* ws;  // B x kProdWs doubles of the handle's workspace
+};
+
 }  // namespace nmpc_impl
+
+// Enqueues the cost-to-go expansions of B scenarios on `stream`: B wavefronts, one per scenario, the
+// nc cases a loop at its end.  Same contract as nmpc_eval_launch.
+int nmpc_policy_value_launch(const nmpc_impl::Params* dprm, int B, int nc, const nmpc_impl::ValIO& io,
+                             void* stream);
 
 // Enqueues the reverse sweep of the closed-loop covariances of B scenarios x nc cases on `stream`:
 // B x nc wavefronts laid out as nmpc_policy_covariance_launch's.  Same contract as nmpc_eval_launch.

@@ -198,6 +198,10 @@ int nmpc_eval_launch(const Params* dprm, int B, const EvalIO& io, void* stream) 
 // the reverse sweep of those rollouts, one lane per sample again: a tenth kernel of this unit
 #include "nmpc_policy_rollout_adjoint.hip"
 
+// the cost-to-go expansion of that policy (expected cost and its variance), one wavefront per
+// scenario: a thirteenth kernel of this unit
+#include "nmpc_policy_value.hip"
+
 // the closed-loop covariance of that policy and its rows' standard deviations, one wavefront per
 // (scenario, case): an eleventh kernel of this unit
 #include "nmpc_policy_covariance.hip"

@@ -5735,7 +5735,7 @@ int nmpc_solve_batch(nmpc_handle* h, int32_t B, const double* x0, int64_t ld_x0,
 }
 
 // ---- the batched entry points at given points.  One argument block, one check, one enqueue and
-// one staging routine serve the twelve entry-point pairs (X_batch on host pointers, X_batch_dev on
+// one staging routine serve the thirteen entry-point pairs (X_batch on host pointers, X_batch_dev on
 // device pointers); a pair adds its own rules, its table of lengths and its launch callback
 struct CallArgs {
   // the inputs in the C argument order (absent ones null) and their leading dimensions
@@ -6496,6 +6496,53 @@ int nmpc_policy_covariance_adjoint_batch(nmpc_handle* h, int32_t B, int32_t nc, 
              nullptr, 0, nc};
   if (int rc = covadj_check(h, B, a)) return rc;
   return staged(h, B, a, covadj_launch, "policy covariance adjoint", 0);
+}
+
+// ---- the cost-to-go expansion of the policy (kernel: nmpc_policy_value.hip): inputs p, ubar, Xbar,
+// K, S0, W; outputs J, lam, P and dJ, varJ of the nc cases.  Workspace as the products kernel's, one
+// slice per scenario
+static int val_check(const nmpc_handle* h, int32_t B, CallArgs& a) {
+  const char* own = nullptr;
+  if (a.n > 0 && !a.in[4]) own = "required pointer is null (S0 with nc > 0)";
+  else if (a.n == 0 && (a.in[4] || a.in[5] || a.out[3] || a.out[4]))
+    own = "nc = 0 takes J_out, lam_out and P_out alone (S0, W, dJ_out and varJ_out must be null)";
+  else if (all_null(a.out, 5)) own = "J_out, lam_out, P_out, dJ_out and varJ_out are all null";
+  return check(h, B, a.n < 0 ? "nc < 0" : nullptr, a, 0x7, "required pointer is null (p, ubar, Xbar)", own,
+               [](const Params& P, CallArgs& a) {
+                 const size_t nw = P.nwE, nx = P.nxE, nu = P.nuE, N = P.N, nc = a.n;
+                 set_lens(a.vlen, {(size_t)P.npE, nw, nx * (N + 1), nu * nx * N, nx * nx * nc, nx * nx * nc});
+                 set_lens(a.olen, {1, nx * (N + 1), nx * nx * (N + 1), nc, nc});
+               });
+}
+static int val_launch(const nmpc_handle* h, int32_t B, const CallArgs& a, void* stream) {
+  ValIO io;
+  io.p = a.in[0]; io.ubar = a.in[1]; io.Xbar = a.in[2]; io.K = a.in[3]; io.S0 = a.in[4]; io.W = a.in[5];
+  io.ld_p = a.ld[0]; io.ld_ubar = a.ld[1]; io.ld_Xbar = a.ld[2]; io.ld_K = a.ld[3]; io.ld_S0 = a.ld[4];
+  io.ld_W = a.ld[5];
+  io.J = a.out[0]; io.lam = a.out[1]; io.P = a.out[2]; io.dJ = a.out[3]; io.varJ = a.out[4];
+  io.ws = h->dws;
+  return nmpc_policy_value_launch(h->dprm, (int)B, (int)a.n, io, stream);
+}
+
+int nmpc_policy_value_batch_dev(nmpc_handle* h, int32_t B, int32_t nc, const double* p, int64_t ld_p,
+                                const double* ubar, int64_t ld_ubar, const double* Xbar, int64_t ld_Xbar,
+                                const double* K, int64_t ld_K, const double* S0, int64_t ld_S0, const double* W,
+                                int64_t ld_W, double* J_out, double* lam_out, double* P_out, double* dJ_out,
+                                double* varJ_out, void* stream) {
+  CallArgs a{{p, ubar, Xbar, K, S0, W}, {ld_p, ld_ubar, ld_Xbar, ld_K, ld_S0, ld_W}, 6,
+             {J_out, lam_out, P_out, dJ_out, varJ_out}, 5, nullptr, 0, nc};
+  if (int rc = val_check(h, B, a)) return rc;
+  return enqueue(h, B, a, stream, val_launch, "policy value", kProdWs);
+}
+
+int nmpc_policy_value_batch(nmpc_handle* h, int32_t B, int32_t nc, const double* p, int64_t ld_p, const double* ubar,
+                            int64_t ld_ubar, const double* Xbar, int64_t ld_Xbar, const double* K, int64_t ld_K,
+                            const double* S0, int64_t ld_S0, const double* W, int64_t ld_W, double* J_out,
+                            double* lam_out, double* P_out, double* dJ_out, double* varJ_out) {
+  CallArgs a{{p, ubar, Xbar, K, S0, W}, {ld_p, ld_ubar, ld_Xbar, ld_K, ld_S0, ld_W}, 6,
+             {J_out, lam_out, P_out, dJ_out, varJ_out}, 5, nullptr, 0, nc};
+  if (int rc = val_check(h, B, a)) return rc;
+  return staged(h, B, a, val_launch, "policy value", kProdWs);
 }
 
 int nmpc_shift_dev(nmpc_handle* h, int32_t B, double* p, int64_t ld_p, const double* u_sol, double* w_out,

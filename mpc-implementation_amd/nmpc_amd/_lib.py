@@ -35,6 +35,7 @@ EXPORTS = (
     "nmpc_solve_policy_batch", "nmpc_solve_policy_batch_dev",
     "nmpc_policy_rollout_batch", "nmpc_policy_rollout_batch_dev",
     "nmpc_policy_rollout_adjoint_batch", "nmpc_policy_rollout_adjoint_batch_dev",
+    "nmpc_policy_value_batch", "nmpc_policy_value_batch_dev",
     "nmpc_policy_covariance_batch", "nmpc_policy_covariance_batch_dev",
     "nmpc_policy_covariance_adjoint_batch", "nmpc_policy_covariance_adjoint_batch_dev",
 )
@@ -145,6 +146,9 @@ def lib():
         L.nmpc_policy_rollout_adjoint_batch.argtypes = ([vp, C.c_int32, C.c_int32] + [dp, i64] * 10 + [dp] * 6 + [i32p])
         L.nmpc_policy_rollout_adjoint_batch_dev.argtypes = ([vp, C.c_int32, C.c_int32] + [vp, i64] * 10 + [vp] * 7
                                                             + [vp])
+    if hasattr(L, "nmpc_policy_value_batch") or not os.environ.get("NMPC_LIB"):
+        L.nmpc_policy_value_batch.argtypes = [vp, C.c_int32, C.c_int32] + [dp, i64] * 6 + [dp] * 5
+        L.nmpc_policy_value_batch_dev.argtypes = [vp, C.c_int32, C.c_int32] + [vp, i64] * 6 + [vp] * 5 + [vp]
     if hasattr(L, "nmpc_policy_covariance_batch") or not os.environ.get("NMPC_LIB"):
         L.nmpc_policy_covariance_batch.argtypes = [vp, C.c_int32, C.c_int32] + [dp, i64] * 7 + [dp] * 3
         L.nmpc_policy_covariance_batch_dev.argtypes = [vp, C.c_int32, C.c_int32] + [vp, i64] * 7 + [vp] * 3 + [vp]

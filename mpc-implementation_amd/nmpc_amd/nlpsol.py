@@ -1209,6 +1209,110 @@ class Solver:
             res["K_bar"] = np.ascontiguousarray(np.swapaxes(res["K_bar"], -1, -2))
         return res
 
+    # ---- the policy's cost-to-go expansion: expected cost and its variance
+    # (nmpc_policy_value_batch)
+    VALUE_OUT = ("J", "lam", "P", "dJ", "varJ")
+
+    def _value_shapes(self, B, nc):
+        N, nu, nx = self._policy_dims()
+        return {"J": (B,), "lam": (B, N + 1, nx), "P": (B, N + 1, nx, nx), "dJ": (B, nc), "varJ": (B, nc)}
+
+    def policy_value_device(self, p, ubar, Xbar, K, S0=None, W=None, out: dict | None = None,
+                            want=("J", "dJ", "varJ"), stream=None):
+        """The local quadratic model of the closed loop's cost-to-go along the plan under the unclamped
+        policy u_k = ubar_k + K_k (x_k - Xbar_k), and from it the expected cost and its variance
+        (``nmpc_policy_value_batch_dev``, whose comment states the recursion), torch CUDA float64
+        tensors in and out.  ``p``, ``ubar``, ``Xbar``, ``K``, ``S0`` and ``W`` as
+        :meth:`policy_covariance_device` takes them (``K`` None: open loop; ``S0`` None: nc = 0, no
+        cases).  Returns a dict with the outputs named in ``want`` and those preallocated in ``out``:
+        ``J`` (B,) the plan's cost, ``lam`` (B,N+1,nx) and ``P`` (B,N+1,nx,nx) the gradient and the
+        exactly symmetric Hessian of the cost-to-go at every stage (stage N's are 0), ``dJ`` (B,nc) with
+        E[J] = J + dJ to second order and ``varJ`` (B,nc) the variance of J to first order; without
+        cases ``dJ`` and ``varJ`` are left out.  Enqueued on ``stream`` (default = current); never
+        synchronises the host and reads nothing back; the handle's workspace serves, grown only when
+        it does not cover B scenarios yet (a solve's does)."""
+        import torch  # plumbing only: device memory and streams
+
+        N, nu, nx = self._policy_dims()
+        if p is None or ubar is None or Xbar is None:
+            raise ValueError("p, ubar and Xbar are required")
+        if S0 is None and W is not None:
+            raise ValueError("W needs S0")
+        nc = 0
+        if S0 is not None:
+            assert S0.dim() in (3, 4) and tuple(S0.shape[-2:]) == (nx, nx), ("S0", tuple(S0.shape))
+            nc = S0.shape[-3]
+        B = None
+        for t, lead in ((S0, 4), (p, 2), (ubar, 2), (Xbar, 3), (W, 4), (K, 4)):
+            if t is not None and t.dim() == lead:
+                B = t.shape[0]
+                break
+        if B is None:
+            raise ValueError("policy_value_device: no argument carries the batch size")
+        if K is not None and tuple(K.shape[-2:]) == (nu, nx):
+            K = K.transpose(-1, -2)  # policy_device's view back to the kernel's column-major blocks
+        ins = _dev_ins((("p", p, (self.np,)), ("ubar", ubar, (self.nw,)), ("Xbar", Xbar, (N + 1, nx)),
+                        ("K", K, (N, nx, nu)), ("S0", S0, (nc, nx, nx)), ("W", W, (nc, nx, nx))), B)
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        shapes = self._value_shapes(B, nc)
+        res = dict(out or {})
+        with torch.cuda.stream(stream):
+            for k in want:
+                if res.get(k) is None and not (nc == 0 and k in ("dJ", "varJ")):
+                    res[k] = torch.empty(shapes[k], dtype=torch.float64, device=Xbar.device)
+        if all(res.get(k) is None for k in self.VALUE_OUT):
+            raise ValueError("policy_value_device: one of " + ", ".join(self.VALUE_OUT) + " is required")
+        ptr = _dev_outs(res, shapes.items())
+        _lib.check(_lib.lib().nmpc_policy_value_batch_dev(self._h, B, nc, *ins, *ptr, _stream_ptr(stream)))
+        return {k: v for k, v in res.items() if v is not None}
+
+    def policy_value(self, p, ubar, Xbar, K, S0=None, W=None, want=("J", "lam", "P", "dJ", "varJ")):
+        """:meth:`policy_value_device` through the host entry point (``nmpc_policy_value_batch``),
+        NumPy arrays in the same scenario-major shapes as :meth:`policy_covariance` takes them: ``K``
+        (B,N,nu,nx) (row-major blocks) or None, ``S0`` (B,nc,nx,nx) or None (no cases) and ``W`` --
+        each may be shared (without the B).  Returns the outputs named in ``want``."""
+        N, nu, nx = self._policy_dims()
+        nc = 0
+        if S0 is not None:
+            S0 = np.ascontiguousarray(S0, dtype=np.float64)
+            if S0.ndim not in (3, 4) or S0.shape[-2:] != (nx, nx):
+                raise ValueError(f"S0: expected (nc,{nx},{nx}) or (B,nc,{nx},{nx}), got shape {S0.shape}")
+            nc = S0.shape[-3]
+        elif W is not None:
+            raise ValueError("W needs S0")
+        if K is not None:
+            K = np.asarray(K, dtype=np.float64)
+            if K.shape[-2:] != (nu, nx):
+                raise ValueError(f"K: expected blocks of ({nu},{nx}), got shape {K.shape}")
+            K = np.swapaxes(K, -1, -2)  # to the kernel's column-major blocks
+        fields = (("p", p, (self.np,)), ("ubar", ubar, (self.nw,)), ("Xbar", Xbar, (N + 1, nx)), ("K", K, (N, nx, nu)),
+                  ("S0", S0, (nc, nx, nx)), ("W", W, (nc, nx, nx)))
+        arrs, B = [], None
+        for name, a, tail in fields:
+            if a is None:
+                if name in ("p", "ubar", "Xbar"):
+                    raise ValueError(f"{name} is required")
+                arrs.append((None, 0))
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape == tail:
+                arrs.append((a, 0))
+                continue
+            if a.shape[1:] != tail or B not in (None, a.shape[0]):
+                raise ValueError(f"{name}: expected {tail} or (B,) + {tail}, got shape {a.shape}")
+            B = a.shape[0]
+            arrs.append((a, int(np.prod(tail))))
+        if B is None:
+            raise ValueError("policy_value: no argument carries the batch size")
+        shapes = self._value_shapes(B, nc)
+        res = {k: np.empty(shapes[k]) for k in self.VALUE_OUT if k in want and not (nc == 0 and k in ("dJ", "varJ"))}
+        if not res:
+            raise ValueError("policy_value: one of " + ", ".join(self.VALUE_OUT) + " is required")
+        ptr = [_dptr(res[k]) if k in res else None for k in self.VALUE_OUT]
+        _lib.check(_lib.lib().nmpc_policy_value_batch(self._h, B, nc, *_flat_ins(arrs), *ptr))
+        return res
+
     # ---- the policy's closed-loop covariance and the rows' standard deviations
     # (nmpc_policy_covariance_batch)
     COVARIANCE_OUT = ("Sigma", "sigma_u", "sigma_g")

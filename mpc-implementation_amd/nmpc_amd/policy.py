@@ -10,8 +10,10 @@ policy, clamped, on the nonlinear plant for many disturbance samples per scenari
 (``Solver.policy_rollout_device``): what it costs and whether it keeps the rows.  :func:`covariance`
 gives what those rollouts estimate in closed form, the state covariance around the plan and the
 standard deviation of every row and control (``Solver.policy_covariance_device``),
-:func:`covariance_grad` its reverse sweep (``Solver.policy_covariance_adjoint_device``), and
-:func:`tighten` moves the bounds of the next solve inwards by a multiple of them."""
+:func:`covariance_grad` its reverse sweep (``Solver.policy_covariance_adjoint_device``),
+:func:`tighten` moves the bounds of the next solve inwards by a multiple of them, and
+:func:`expected_cost` gives the policy's expected cost and its variance to second order
+(``Solver.policy_value_device``)."""
 from __future__ import annotations
 
 
@@ -138,6 +140,30 @@ def covariance(solver, pol: dict, sol: dict, p, S0, W=None, obs_var=None, c=None
     raw = pol["raw"]
     return solver.policy_covariance_device(p, ubar.contiguous(), raw["X"], raw["K"] if feedback else None, S0, W=W,
                                            obs_var=obs_var, out=out, want=want, stream=stream)
+
+
+def expected_cost(solver, pol: dict, sol: dict, p, S0, W=None, feedback: bool = True, out: dict | None = None,
+                  want=("J", "dJ", "varJ"), stream=None):
+    """The expected cost of the unclamped policy under an uncertain initial state and process noise, to
+    second order, in one launch (``Solver.policy_value_device``): the number the mean of
+    :func:`rollout`'s sampled J estimates, without the sampling noise.  ``S0`` (B, nc, nx, nx) or (nc,
+    nx, nx) holds one covariance of the initial state per case and ``W`` likewise the process noise
+    added at every stage (None: none), as :func:`covariance` takes them; ``feedback=False`` expands the
+    open loop.  Returns the dict of ``Solver.policy_value_device``: ``J`` (B,) the plan's own cost,
+    ``dJ`` (B, nc) the second-order shift of its mean, ``varJ`` (B, nc) its variance to first order
+    and, when asked for in ``want`` or preallocated in ``out``, ``lam`` (B, N+1, nx) and ``P`` (B, N+1,
+    nx, nx), the gradient and Hessian of the cost-to-go at every stage; with ``J`` and ``dJ`` both
+    there, also ``EJ`` (B, nc) = J + dJ.
+    The expansion is taken at ``pol``'s states and ``sol``'s controls, which are the closed loop's own
+    undisturbed trajectory.  There is no parameter move ``c`` here: after one the plan's states are no
+    longer the trajectory of the moved controls, and the first-order terms this expansion leaves out
+    would not vanish.  Nothing is copied to the host and nothing synchronises."""
+    raw = pol["raw"]
+    res = solver.policy_value_device(p, sol["x"].contiguous(), raw["X"], raw["K"] if feedback else None, S0=S0, W=W,
+                                     out=out, want=want, stream=stream)
+    if res.get("J") is not None and res.get("dJ") is not None:
+        res["EJ"] = res["J"].unsqueeze(1) + res["dJ"]
+    return res
 
 
 def var_seed(sigma, sigma_b):
